@@ -23,7 +23,18 @@ with its code. Rank 0 prints one JSON line:
 * ``positions_per_s`` -- all ``global_batch * Nmax`` decoder positions per
   second (the Magenta recipe trains the pen-state loss on every padded
   position too, so these are loss targets; round 1 reported this number as
-  ``value``).
+  ``value``);
+* ``ms_per_step`` -- wall milliseconds per timed step (``--steps`` of them).
+
+A plain run sets up, warms up, times the steps and prints the line. ``--full``
+adds what the headline figure does not need: the evaluation of the held-out
+split after the timed steps (``test_recon_nll``; ``--no-eval`` skips it there
+too). ``--dump-outputs DIR`` writes what the last timed step produced, as
+``DIR/<name>.npy`` (float32): the loss scalars ``train_step`` returns, and the
+parameters and gradients the step leaves in the optimizer's arena (a fixed,
+seeded sample of ``DUMP_SAMPLE`` elements each when the arena is larger). Data,
+initial weights and noise are seeded, so the same arguments give the same
+inputs from run to run.
 """
 from __future__ import annotations
 
@@ -58,6 +69,27 @@ def _launch_ranks(n: int) -> int:
     return subprocess.call(cmd)
 
 
+DUMP_SAMPLE = 1 << 22   # elements kept of each arena array (16 MB as float32)
+
+
+def _dump_outputs(path: str, out, opt) -> None:
+    """Write the last timed step's results as ``<path>/<name>.npy`` (float32):
+    every tensor ``train_step`` returned, and the parameter / gradient arenas
+    it updated (``DUMP_SAMPLE`` elements at fixed seeded offsets when larger)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            np.save(os.path.join(path, "%s.npy" % k), v.detach().to("cpu", torch.float32).numpy())
+    n = opt.numel
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.as_tensor(np.sort(np.random.default_rng(2024).integers(0, n, size=DUMP_SAMPLE)))
+    for name, arena in (("params", opt.flat), ("grads", opt.grad)):
+        a = arena.detach() if idx is None else arena.detach()[idx.to(arena.device)]
+        np.save(os.path.join(path, "%s.npy" % name), a.to("cpu", torch.float32).numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -69,7 +101,11 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["fp32", "bf16"])
     ap.add_argument("--backend", default="auto", choices=["auto", "hip", "torch"])
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-eval", action="store_true")
+    ap.add_argument("--no-eval", action="store_true", help="with --full: skip the held-out evaluation")
+    ap.add_argument("--full", action="store_true", help="also evaluate the held-out split after the timed "
+                    "steps (test_recon_nll); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--trace", action="store_true", help="print every step's cost to stderr (syncs each step)")
     ap.add_argument("--sketches", type=int, default=2000)
     ap.add_argument("--dist-backend", default=None, help="override (default: nccl = RCCL on GPUs); "
@@ -146,8 +182,10 @@ def main():
         check_device_faults()   # a timed-out in-launch exchange invalidates the run: fail loudly
     # global mean over ranks (reduced with the last gradient bucket) under DP
     cost = trainer.reduced_scalars()["cost"] if trainer.reducer is not None else float(out["cost"])
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, out, trainer.opt)
     recon = None
-    if not args.no_eval:
+    if args.full and not args.no_eval:
         ev = trainer.evaluate(test)      # the whole held-out split (test.num_batches batches)
         recon = ev["r_cost"]
     probe = next(trainer.model.parameters())
@@ -198,7 +236,8 @@ def main():
             "valid_fraction": round(value / positions_per_s, 4),
             "train_cost": round(cost, 4),
             "test_recon_nll": None if recon is None else round(recon, 4),
-            "test_recon_nll_note": "mean over the full synthetic test split (%d sketches) after %d random-init "
+            "test_recon_nll_note": "not measured: the held-out evaluation runs with --full" if recon is None else
+                                   "mean over the full synthetic test split (%d sketches) after %d random-init "
                                    "training steps: a smoke value, not a quality result (see profiles/ for "
                                    "the convergence runs)" % (test.num_batches * args.batch, args.warmup + args.steps),
         }

@@ -187,6 +187,42 @@ def test_bench_multi_rank_cpu(tmp_path):
     assert 0 < rec["value"] <= rec["positions_per_s"] and 0 < rec["valid_fraction"] <= 1
 
 
+def test_bench_plain_full_and_dump_cpu(tmp_path):
+    """bench.py on the CPU: a plain run times ``--steps`` steps and skips the
+    held-out evaluation, ``--full`` runs it, and ``--dump-outputs`` writes the
+    last timed step's losses / parameters / gradients as float32 ``.npy``
+    files that a second run with the same inputs (here the ``--full`` one)
+    reproduces."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+            "--config", "plumbing", "--batch", "4", "--seq-len", "24", "--sketches", "60", "--dtype", "fp32",
+            "--backend", "torch"]
+    env = dict(os.environ, OMP_NUM_THREADS="1", CUDA_VISIBLE_DEVICES="")
+
+    def run(extra):
+        p = subprocess.run(base + extra, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        return json.loads(lines[0])
+
+    rec = run(["--dump-outputs", str(tmp_path / "a")])
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["test_recon_nll"] is None
+    assert rec["unit"] == "strokes/s" and rec["higher_is_better"] is True and rec["dtype"] == "fp32"
+    full = run(["--full", "--dump-outputs", str(tmp_path / "b")])
+    assert full["test_recon_nll"] is not None and np.isfinite(full["test_recon_nll"])
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert {"cost.npy", "r_cost.npy", "kl_cost.npy", "params.npy", "grads.npy"} <= set(names)
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, b), n
+    assert np.load(tmp_path / "a" / "params.npy").size > 1000 and np.abs(np.load(tmp_path / "a" / "grads.npy")).max() > 0
+
+
 def _scalars_worker(rank, world, port, out_dir, wire="fp32"):
     """The loss scalars packed into the arena tail come out of the last
     bucket as the sum over ranks: the trainer's logged cost is the mean of

@@ -17,7 +17,8 @@ from sketch_rnn_amd.train import schedules
 from sketch_rnn_amd.train.optim import FlatAdam, adam_reference_step
 from sketch_rnn_amd.utils import safe_pickle
 
-REF_PKL = "/root/reference/save/kanji/config.pkl"
+# the reference's saved kanji run configuration (a protocol-2 pickle of its argparse namespace)
+REF_PKL = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_kanji_config.pkl")
 
 
 def _params(seed=0):
@@ -120,7 +121,6 @@ def test_config_json_roundtrip_and_presets(tmp_path):
     assert PRESETS["vae_classcond"].num_classes == 345
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PKL), reason="reference tree not present")
 def test_reference_config_pkl_safe_reader():
     cfg = RefConfig.from_config_pkl(REF_PKL)
     assert (cfg.rnn_size, cfg.num_layers, cfg.model, cfg.num_mixture, cfg.seq_length) == (256, 2, "lstm", 24, 300)
