@@ -1,4 +1,5 @@
-"""Fused whole-sketch decoder for the reference model (``csrc/decode_ref.hip``).
+"""Fused whole-sketch decoders: the reference model (``csrc/decode_ref.hip``)
+and the VAE's plain LSTM decoders (``csrc/decode_vae.hip``).
 
 The reference samples one stroke per ``sess.run`` (``model.py:187-264``:
 two host transfers per stroke, ~486 strokes/s here). :class:`GraphDecoder`
@@ -15,6 +16,15 @@ random numbers, the reference's pen-temperature bug unless
 finished rows), with bf16 MFMA operands and fp32 state. Eligible models:
 ``lstm`` cells, ``rnn_size`` 256, 1 or 2 layers, at most 32 mixtures
 (:func:`fused_decode_ok`); anything else keeps using ``GraphDecoder``.
+
+:class:`FusedVAEDecoder` does the same for a :class:`SketchVAE` whose decoder
+is a plain ``lstm`` of size 256 (up to 32 mixtures) or 512 (up to 20)
+(:func:`fused_vae_ok`): one launch per chunk of steps and rows, with the
+latent's input projection folded into a per-row bias, an all-done exit
+between chunks, and per-row stroke prefixes (sketch completion).
+``layer_norm`` decoders (row statistics over all 4H gate columns would need
+a cross-workgroup exchange per stroke) and ``hyper`` decoders stay on
+``GraphDecoder``.
 """
 from __future__ import annotations
 
@@ -41,11 +51,23 @@ class NotCoResident(RuntimeError):
     (``skr_decode_ref`` returned -8); callers fall back to ``GraphDecoder``."""
 
 
-def _chunk_rows(L: int, mtw: int, cus: int = 256) -> int:
+def fused_vae_ok(model) -> bool:
+    """A :class:`SketchVAE` with a plain ``lstm`` decoder that
+    ``csrc/decode_vae.hip`` takes: ``dec_rnn_size`` 256 with at most 32
+    mixtures, or 512 with at most 20 (the head's weights must fit in LDS).
+    Conditional, unconditional and class-conditional models all qualify."""
+    from ..models.vae import SketchVAE
+    if not isinstance(model, SketchVAE) or model.cfg.dec_model != "lstm":
+        return False
+    H, M = model.cfg.dec_rnn_size, model.cfg.num_mixture
+    return (H == 256 and 1 <= M <= 32) or (H == 512 and 1 <= M <= 20)
+
+
+def _chunk_rows(L: int, mtw: int, cus: int = 256, H: int = _H) -> int:
     """Rows one launch can take: every workgroup must be co-resident (one
-    ~100 KB-LDS workgroup per CU, ``cus`` CUs -- 256 on MI355X; L*16 + 1
+    ~100 KB-LDS workgroup per CU, ``cus`` CUs -- 256 on MI355X; L*(H/16) + 1
     workgroups per row block)."""
-    return (cus // (L * (_H // 16) + 1)) * 16 * mtw
+    return (cus // (L * (H // 16) + 1)) * 16 * mtw
 
 
 class FusedRefDecoder:
@@ -183,3 +205,207 @@ class FusedRefDecoder:
         z = torch.cat(zs, 1)
         check_cluster_errors(self.dev)
         return z
+
+
+class FusedVAEDecoder:
+    """B sketches of N strokes from a :class:`SketchVAE` with a plain ``lstm``
+    decoder (``csrc/decode_vae.hip``): the LSTM layer, the MDN head and the
+    sampler of every step of ``chunk`` steps in one launch per chunk of rows.
+
+    Semantics are those of ``GraphDecoder`` in VAE mode (start token
+    ``[0, 0, 1, 0, 0]``, identical hash random numbers, temperature on
+    mixture, pen and sigma, end-of-sketch padding of finished rows), with
+    bf16 MFMA operands and fp32 state. After each chunk of steps the host
+    reads whether every row has ended; if so the remaining chunks are not
+    launched and their strokes are filled with padding (``steps_run`` records
+    the steps executed). Chunking does not change a single bit of the result.
+    ``layer_norm`` and ``hyper`` decoders are not eligible
+    (:func:`fused_vae_ok`); they keep using ``GraphDecoder``.
+    """
+
+    def __init__(self, model, batch: int, steps: int, temperature: float = 1.0, greedy: bool = False,
+                 chunk: int = 50, early_exit: bool = True):
+        if not fused_vae_ok(model):
+            raise ValueError("FusedVAEDecoder: needs a SketchVAE with an lstm decoder of size 256 (M <= 32) "
+                             "or 512 (M <= 20)")
+        self.lib = native.require_hip()
+        self.model = model
+        self.B, self.N = int(batch), int(steps)
+        self.temp, self.greedy = float(temperature), bool(greedy)
+        cfg = model.cfg
+        self.H, self.M = cfg.dec_rnn_size, cfg.num_mixture
+        self.nout = 3 + 6 * self.M
+        self.noutp = -(-self.nout // 16) * 16
+        self.dev = next(model.parameters()).device
+        cus = torch.cuda.get_device_properties(self.dev).multi_processor_count if self.dev.type == "cuda" else 256
+        self.rows = _chunk_rows(1, 1 if self.B <= 16 else 2, cus, self.H)
+        if self.rows <= 0:
+            raise NotCoResident("FusedVAEDecoder: %d CUs cannot hold one row block (%d workgroups)"
+                                % (cus, self.H // 16 + 1))
+        c = max(int(chunk), 1)
+        self.ranges = [(t, min(t + c, self.N)) for t in range(0, self.N, c)]
+        self.early_exit = bool(early_exit)
+        self.steps_run = 0
+        self.seed = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        self._w = None
+        self._sig = None
+
+    # -- weights (bf16 operands, refreshed when the parameters change) -------------------
+    @torch.no_grad()
+    def _weights(self):
+        sig = tuple(p._version for p in self.model.parameters()) + tuple(p.data_ptr() for p in self.model.parameters())
+        if self._w is not None and sig == self._sig:
+            return self._w
+        m, bf, p = self.model, torch.bfloat16, self.model.dec
+        WoT = torch.zeros(self.noutp, self.H, dtype=bf, device=self.dev)
+        WoT[: self.nout] = m.output_w.detach().t().to(bf)
+        Wx = p.W_x.detach().float()
+        self._w = {
+            "WT": p.W_h.detach().t().to(bf).contiguous(),            # [4H, H]
+            "Wx": Wx[:5].contiguous(),                               # [5, 4H] stroke rows
+            "Wz": Wx[5:].contiguous(),                               # [z_in, 4H] rows of the conditioning
+            "b": p.bias.detach().float().contiguous(),
+            "WoT": WoT,
+            "bo": m.output_b.detach().float().contiguous(),
+        }
+        self._sig = sig
+        return self._w
+
+    def _latent(self, seed: int, z, labels):
+        """``(zc, (h0, c0))`` as ``GraphDecoder`` conditions a run."""
+        cfg, B, dev = self.model.cfg, self.B, self.dev
+        if cfg.conditional:
+            if z is None:
+                g = torch.Generator(device=dev).manual_seed(int(seed))
+                z = torch.randn((B, max(cfg.z_size, 1)), device=dev, generator=g)
+            z = z.to(dev, torch.float32)
+        lab = None
+        if cfg.num_classes > 0:
+            lab = torch.zeros(B, dtype=torch.int64, device=dev) if labels is None else labels.to(dev, torch.int64)
+        zc = self.model.condition(z if cfg.conditional else None, lab, B, dev)
+        return zc, self.model.initial_state(zc, B, dev)
+
+    def _begin(self, seed: int, z, labels, xin: torch.Tensor, nforced: Optional[torch.Tensor], want_z: bool):
+        """Buffers of one decode: whole-batch ones the launches index by row
+        slice, and per-launch-chunk ones laid out ``[step][row of the chunk]``."""
+        w = self._weights()
+        B, N, H, dev, f32 = self.B, self.N, self.H, self.dev, torch.float32
+        zc, (h0, c0) = self._latent(seed, z, labels)
+        zb = (zc.to(f32) @ w["Wz"] + w["b"]) if zc is not None else w["b"].expand(B, 4 * H)
+        st = {
+            "zb": zb.contiguous(), "c": c0.to(f32).contiguous().clone(),
+            "out": torch.empty(B, N, 5, dtype=f32, device=dev),
+            "done": torch.zeros(B, dtype=torch.int32, device=dev),
+            "nforced": nforced.to(dev, torch.int32).contiguous() if nforced is not None else None,
+            "chunks": [],
+        }
+        h0 = h0.to(torch.bfloat16)
+        for r0 in range(0, B, self.rows):
+            Bc = min(self.rows, B - r0)
+            mtw = 1 if Bc <= 16 else 2
+            nrb = -(-Bc // (16 * mtw))
+            hbuf = torch.empty(N + 1, Bc, H, dtype=torch.bfloat16, device=dev)
+            hbuf[0] = h0[r0:r0 + Bc]
+            st["chunks"].append({
+                "r0": r0, "Bc": Bc, "mtw": mtw, "nrb": nrb, "hbuf": hbuf,
+                "xin": xin[:, r0:r0 + Bc].contiguous(),
+                "zout": torch.zeros(N, Bc, self.nout, dtype=f32, device=dev) if want_z else None,
+                "flags": torch.empty(nrb * _FLAG_STRIDE, dtype=torch.int32, device=dev),   # zeroed by the launcher
+            })
+        return st
+
+    def _launch(self, st, ch, t0: int, t1: int):
+        from ..ops._hipapi import DecVaeArgs
+        from ..ops.recurrent import cluster_error_flag
+        w = self._weights()
+        r0, Bc = ch["r0"], ch["Bc"]
+        a = DecVaeArgs()
+        a.N, a.B, a.H, a.mtw, a.nrb = self.N, Bc, self.H, ch["mtw"], ch["nrb"]
+        a.M, a.nout, a.noutp, a.greedy, a.row0 = self.M, self.nout, self.noutp, int(self.greedy), int(r0)
+        a.t0, a.t1, a.temp, a.forget_bias = int(t0), int(t1), self.temp, 1.0
+        a.WT, a.Wx, a.WoT, a.bo = w["WT"].data_ptr(), w["Wx"].data_ptr(), w["WoT"].data_ptr(), w["bo"].data_ptr()
+        a.zb = st["zb"][r0:].data_ptr()
+        a.c0 = a.cT = st["c"][r0:].data_ptr()
+        a.hbuf, a.xin = ch["hbuf"].data_ptr(), ch["xin"].data_ptr()
+        a.out, a.done = st["out"][r0:].data_ptr(), st["done"][r0:].data_ptr()
+        a.nforced = st["nforced"][r0:].data_ptr() if st["nforced"] is not None else None
+        a.zout = ch["zout"].data_ptr() if ch["zout"] is not None else None
+        a.seed, a.flags = self.seed.data_ptr(), ch["flags"].data_ptr()
+        a.err = cluster_error_flag(self.dev).data_ptr()
+        rc = self.lib.lib.skr_decode_vae(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc == -8:
+            raise NotCoResident("skr_decode_vae: workgroups cannot be co-resident on this device (code -8)")
+        if rc != 0:
+            raise RuntimeError("skr_decode_vae: launch failed (code %d)" % rc)
+
+    @torch.no_grad()
+    def run(self, seed: int = 0, z: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
+            prefix: Optional[torch.Tensor] = None, prefix_len: Optional[torch.Tensor] = None,
+            return_z: bool = False):
+        """Returns ``(strokes [B, N, 5], lengths [B])`` like
+        :meth:`GraphDecoder.run` (plus the head outputs ``z [N, B, 3+6M]`` with
+        ``return_z``; steps an early exit skipped are zero there).
+
+        ``prefix [B, P, 5]`` with ``prefix_len [B]`` (default P for every row)
+        completes sketches: the first ``prefix_len[b]`` strokes of row b are
+        the prefix's and the decoder continues from them."""
+        from ..ops.recurrent import check_cluster_errors
+        B, N, dev = self.B, self.N, self.dev
+        self.seed.fill_(int(seed))
+        xin = torch.zeros(N + 1, B, _XLD, device=dev)
+        xin[0, :, 2] = 1.0                                          # start token
+        nforced = None
+        if prefix is not None:
+            prefix = prefix.to(dev, torch.float32)
+            P = prefix.shape[1]
+            plen = (torch.full((B,), P, dtype=torch.int64, device=dev) if prefix_len is None
+                    else torch.as_tensor(prefix_len).to(dev, torch.int64))
+            if prefix.shape[0] != B or prefix.shape[2] != 5 or plen.shape != (B,):
+                raise ValueError("FusedVAEDecoder.run: prefix must be [B, P, 5] and prefix_len [B]")
+            if bool((plen < 0).any()) or bool((plen > min(P, N)).any()):
+                raise ValueError("FusedVAEDecoder.run: prefix_len must lie in [0, min(P, steps)]")
+            inside = torch.arange(P, device=dev)[None, :] < plen[:, None]
+            if bool((inside & (prefix[:, :, 4] > 0)).any()):
+                raise ValueError("FusedVAEDecoder.run: a prefix ends its sketch (pen state 4) inside its length")
+            Pn = min(P, N)
+            xin[1:Pn + 1, :, :5] = (prefix[:, :Pn] * inside[:, :Pn, None]).transpose(0, 1)
+            nforced = plen
+        st = self._begin(seed, z, labels, xin, nforced, return_z)
+        ran = N
+        for t0, t1 in self.ranges:
+            for ch in st["chunks"]:
+                self._launch(st, ch, t0, t1)
+            ran = t1
+            if self.early_exit and t1 < N and bool(st["done"].all()):   # one host read per chunk of steps
+                break
+        strokes = st["out"]
+        if ran < N:            # strokes the skipped launches would have drawn: all padding
+            strokes[:, ran:] = 0.0
+            strokes[:, ran:, 4] = 1.0
+        self.steps_run = ran
+        check_cluster_errors(dev)
+        hits = strokes[:, :, 4] > 0
+        lengths = torch.where(hits.any(1), hits.float().argmax(1) + 1,
+                              torch.full_like(hits[:, 0], N, dtype=torch.long))
+        if return_z:
+            return strokes, lengths, torch.cat([ch["zout"] for ch in st["chunks"]], 1)
+        return strokes, lengths
+
+    @torch.no_grad()
+    def forced(self, xs: torch.Tensor, z: Optional[torch.Tensor] = None,
+               labels: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Teacher-forced decode: ``xs [N, B, 5]`` fed inputs (``xs[0]`` the
+        start token) -> head outputs ``z [N, B, 3+6M]`` (the kernel's numerics
+        against the step oracle). ``z`` None on a conditional model draws the
+        latent as ``run(seed=0)`` does."""
+        from ..ops.recurrent import check_cluster_errors
+        N, B = xs.shape[0], xs.shape[1]
+        assert N == self.N and B == self.B
+        self.seed.fill_(0)
+        xin = torch.zeros(N + 1, B, _XLD, device=self.dev)
+        xin[:N, :, :5] = xs.to(self.dev, torch.float32)
+        st = self._begin(0, z, labels, xin, torch.full((B,), N, dtype=torch.int32, device=self.dev), True)
+        for ch in st["chunks"]:
+            self._launch(st, ch, 0, N)
+        check_cluster_errors(self.dev)
+        return torch.cat([ch["zout"] for ch in st["chunks"]], 1)

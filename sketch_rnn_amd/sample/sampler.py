@@ -19,8 +19,9 @@ writes the next input on device) captured once into a HIP graph and
 replayed; finished rows emit end-of-sketch padding. No host round trip per
 stroke (the reference does two ``sess.run`` transfers per stroke). HyperLSTM
 decoders step through :class:`~.hyper_step.HyperStepDecoder` (state in
-place, seven hand-written kernels per stroke); the reference model has a
-one-launch whole-sketch decoder in :mod:`.fused`.
+place, seven hand-written kernels per stroke); the reference model and
+the VAE's plain ``lstm`` decoders have whole-sketch decoders in
+:mod:`.fused` (the VAE one is opt-in: ``vae_sample --fused``).
 """
 from __future__ import annotations
 
