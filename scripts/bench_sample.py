@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Generation throughput: temperature-sampled decode of the VAE decoder.
 
-``--impl fused`` times the whole-sketch kernel (``FusedVAEDecoder``, plain
-``lstm`` decoders) in place of ``GraphDecoder``; both report the same fields.
+``--impl fused`` times the whole-sketch kernel (``fused_vae_decoder``: plain
+``lstm`` and ``layer_norm`` decoders) in place of ``GraphDecoder``, falling
+back to it with a printed reason for a model or device the kernels do not
+take; both report the same fields.
 
 Compares (a) the HIP-graph batched decoder (``GraphDecoder``: decoder step
 kernels + MDN head + device sampler kernel, captured in chunks of steps with
@@ -46,7 +48,8 @@ def main():
     ap.add_argument("--no-early-exit", action="store_true")
     ap.add_argument("--fp8", action="store_true", help="MX-fp8 h W_h in the HyperLSTM step decoder (BASELINE config 5)")
     ap.add_argument("--impl", default="graph", choices=["graph", "fused"],
-                    help="graph: GraphDecoder; fused: the whole-sketch kernel (FusedVAEDecoder, plain lstm decoders)")
+                    help="graph: GraphDecoder; fused: the whole-sketch kernel (fused_vae_decoder: plain lstm and "
+                         "layer_norm decoders)")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -75,10 +78,16 @@ def main():
         model = tr.model.eval()
     else:
         model = SketchVAE(cfg, seed=0).cuda().eval()
+    dec, impl = None, a.impl
     if a.impl == "fused":
-        from sketch_rnn_amd.sample.fused import FusedVAEDecoder
-        dec = FusedVAEDecoder(model, a.batch, a.steps, a.temperature, early_exit=not a.no_early_exit)
-    else:
+        from sketch_rnn_amd.sample.fused import NotCoResident, fused_vae_decoder
+        try:
+            dec = fused_vae_decoder(model, a.batch, a.steps, a.temperature, early_exit=not a.no_early_exit)
+            dec.run(seed=0)
+        except (ValueError, NotCoResident) as e:
+            print("--impl fused: %s; using the graph decoder" % e, file=sys.stderr)
+            dec, impl = None, "graph"
+    if dec is None:
         dec = GraphDecoder(model, a.batch, a.steps, a.temperature, early_exit=not a.no_early_exit, fp8=a.fp8)
     dec.run(seed=0)  # capture
     torch.cuda.synchronize()
@@ -99,7 +108,7 @@ def main():
     host_sps = a.host_steps / hdt
     valid_sps = total_len / wall
     print(json.dumps({"metric": "sampled valid strokes/sec (temperature %.2f)" % a.temperature, "config": a.config,
-                      "impl": a.impl, "dtype": a.dtype, "fp8_gemm": bool(a.fp8), "batch": a.batch, "steps": a.steps, "train_steps": a.train_steps,
+                      "impl": impl, "dtype": a.dtype, "fp8_gemm": bool(a.fp8), "batch": a.batch, "steps": a.steps, "train_steps": a.train_steps,
                       "train_cost": train_cost, "early_exit": not a.no_early_exit,
                       "valid_strokes_per_s": round(valid_sps, 1),
                       "decode_positions_per_s": round(total_pos / wall, 1),

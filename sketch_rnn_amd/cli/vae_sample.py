@@ -4,9 +4,10 @@ Modes: ``random`` (z ~ N(0, I), or the unconditional decoder), ``class``
 (class-conditional z for ``--label``), ``interpolate`` (spherical
 interpolation between two random latents). Writes a stroke-3 SVG grid.
 ``--device_sampler`` decodes the whole grid in parallel through the
-HIP-graph decoder; with ``--fused`` a plain ``lstm`` decoder of size 256 or
-512 runs through the whole-sketch kernel (``sample.fused.FusedVAEDecoder``)
-instead, and anything it does not take falls back to the graph decoder.
+HIP-graph decoder; with ``--fused`` a plain ``lstm`` or ``layer_norm``
+decoder of size 256 or 512 runs through its whole-sketch kernel
+(``sample.fused.fused_vae_decoder``) instead, and anything those do not take
+falls back to the graph decoder.
 """
 from __future__ import annotations
 
@@ -42,11 +43,12 @@ def main(argv=None) -> int:
                    help="device sampler: h W_h of the HyperLSTM decoder as an MX-fp8 GEMM (BASELINE config 5; "
                         "pays at >= 1024 sketches per call)")
     p.add_argument("--fused", action="store_true",
-                   help="device sampler: decode plain lstm decoders (size 256 with <= 32 mixtures, 512 with <= 20) "
-                        "with the whole-sketch kernel instead of the graph decoder (needs --device_sampler). "
-                        "Measured on vae_small: faster than the graph decoder for --n 1 to 672 (2.7x at 128), "
-                        "slower at 1024 (one launch takes 224 rows at size 512; larger grids run as successive "
-                        "launches)")
+                   help="device sampler: decode plain lstm and layer_norm decoders (size 256 with <= 32 mixtures, 512 "
+                        "with <= 20) with their whole-sketch kernel instead of the graph decoder (needs "
+                        "--device_sampler). Measured on vae_small (lstm): faster than the graph decoder for --n 1 to "
+                        "672 (2.7x at 128), slower at 1024. Measured on vae_layernorm: faster for --n 1, 128 (1.9x) "
+                        "and 448 (1.05x), slower at 1024 (0.55x); one launch takes 224 rows at size 512 and larger "
+                        "grids run as successive launches, so expect it to lose from 3 launches (--n > 448) on")
     a = p.parse_args(argv)
     if a.fused and not a.device_sampler:
         p.error("--fused needs --device_sampler")
@@ -77,16 +79,15 @@ def main(argv=None) -> int:
         zt, lt = torch.as_tensor(zs, dtype=torch.float32, device=device), torch.as_tensor(labels, device=device)
         s = None
         if a.fused:
-            from ..sample.fused import FusedVAEDecoder, NotCoResident, fused_vae_ok
-            if not fused_vae_ok(model):
-                print("--fused: needs an lstm decoder of size 256 (<= 32 mixtures) or 512 (<= 20); "
+            from ..sample.fused import NotCoResident, fused_vae_decoder
+            try:
+                s, _ = fused_vae_decoder(model, a.n, cfg.max_seq_len, a.temperature, a.greedy).run(
+                    seed=a.seed, z=zt, labels=lt)
+            except ValueError:
+                print("--fused: needs an lstm or layer_norm decoder of size 256 (<= 32 mixtures) or 512 (<= 20); "
                       "using the graph decoder")
-            else:
-                try:
-                    s, _ = FusedVAEDecoder(model, a.n, cfg.max_seq_len, a.temperature, a.greedy).run(
-                        seed=a.seed, z=zt, labels=lt)
-                except NotCoResident as e:
-                    print("--fused: %s; using the graph decoder" % e)
+            except NotCoResident as e:
+                print("--fused: %s; using the graph decoder" % e)
         if s is None:
             dec = GraphDecoder(model, a.n, cfg.max_seq_len, a.temperature, a.greedy, fp8=a.fp8)
             s, _ = dec.run(seed=a.seed, z=zt, labels=lt)

@@ -269,6 +269,21 @@ class DecVaeArgs(C.Structure):
     ]
 
 
+class DecVaeLnArgs(C.Structure):
+    """Mirror of ``DecVaeLnArgs`` in csrc/decode_vae_ln.hip (fused whole-sketch LayerNorm-LSTM VAE decoder)."""
+    _fields_ = [
+        ("N", _i), ("B", _i), ("H", _i), ("mtw", _i), ("nrb", _i), ("M", _i), ("nout", _i), ("noutp", _i),
+        ("greedy", _i), ("row0", _i), ("t0", _i), ("t1", _i),
+        ("temp", _f), ("forget_bias", _f),
+        ("WT", _p), ("Wx", _p), ("zp", _p), ("ln_g", _p), ("ln_b", _p), ("lnc_g", _p), ("lnc_b", _p),
+        ("c0", _p), ("cT", _p), ("hbuf", _p),
+        ("WoT", _p), ("bo", _p),
+        ("xin", _p), ("out", _p), ("done", _p), ("nforced", _p), ("zout", _p),
+        ("gstat", _p), ("cstat", _p),
+        ("seed", _p), ("flags", _p), ("err", _p),
+    ]
+
+
 class GemmProblem(C.Structure):
     """Mirror of ``GemmProblem`` in csrc/skinny_gemm.hip."""
     _fields_ = [
@@ -490,6 +505,8 @@ class HipLib:
         lib.skr_decode_ref.restype = _i
         lib.skr_decode_vae.argtypes = [C.POINTER(DecVaeArgs), _p]
         lib.skr_decode_vae.restype = _i
+        lib.skr_decode_vae_ln.argtypes = [C.POINTER(DecVaeLnArgs), _p]
+        lib.skr_decode_vae_ln.restype = _i
         for name, cls in (("skr_lstm_fwd_args_size", LstmFwdArgs), ("skr_lstm_bwd_args_size", LstmBwdArgs),
                           ("skr_gru_fwd_args_size", GruFwdArgs), ("skr_gru_bwd_args_size", GruBwdArgs),
                           ("skr_lstm_fused_fwd_args_size", FusedFwdArgs),
@@ -501,6 +518,7 @@ class HipLib:
                           ("skr_mdn_head_dw_args_size", HeadDw),
                           ("skr_decode_ref_args_size", DecArgs),
                           ("skr_decode_vae_args_size", DecVaeArgs),
+                          ("skr_decode_vae_ln_args_size", DecVaeLnArgs),
                           ("skr_gemm_problem_size", GemmProblem),
                           ("skr_decode_sample_size", DecodeSample),
                           ("skr_chain_sync_size", ChainSync),

@@ -1,5 +1,6 @@
 """Fused whole-sketch decoders: the reference model (``csrc/decode_ref.hip``)
-and the VAE's plain LSTM decoders (``csrc/decode_vae.hip``).
+and the VAE's plain and LayerNorm LSTM decoders (``csrc/decode_vae.hip``,
+``csrc/decode_vae_ln.hip``).
 
 The reference samples one stroke per ``sess.run`` (``model.py:187-264``:
 two host transfers per stroke, ~486 strokes/s here). :class:`GraphDecoder`
@@ -22,9 +23,12 @@ is a plain ``lstm`` of size 256 (up to 32 mixtures) or 512 (up to 20)
 (:func:`fused_vae_ok`): one launch per chunk of steps and rows, with the
 latent's input projection folded into a per-row bias, an all-done exit
 between chunks, and per-row stroke prefixes (sketch completion).
-``layer_norm`` decoders (row statistics over all 4H gate columns would need
-a cross-workgroup exchange per stroke) and ``hyper`` decoders stay on
-``GraphDecoder``.
+:class:`FusedLNVAEDecoder` (``csrc/decode_vae_ln.hip``) is the same decoder
+for ``layer_norm`` decoders of those sizes (:func:`fused_vae_ln_ok`): the
+row statistics of the two layer norms span all workgroups of a row block, so
+each step exchanges per-row partial sums between them inside the launch.
+:func:`fused_vae_decoder` returns the class that takes a model. ``hyper``
+decoders stay on ``GraphDecoder``.
 """
 from __future__ import annotations
 
@@ -37,7 +41,13 @@ from ..utils import native
 
 _H = 256
 _FLAG_STRIDE = 64
+_LN_FLAG_STRIDE = 128      # csrc/decode_vae_ln.hip kLnFlagStride: h | head | gate statistics | cell statistics
 _XLD = 8
+
+# Debug knob of FusedLNVAEDecoder: NaN-fill every in-launch hand-off buffer
+# (statistics slots, hbuf[1:], the rows of xin[1:] no prefix supplies) before
+# each run. Results must not change.
+LN_DECODE_POISON = False
 
 
 def fused_decode_ok(model) -> bool:
@@ -61,6 +71,27 @@ def fused_vae_ok(model) -> bool:
         return False
     H, M = model.cfg.dec_rnn_size, model.cfg.num_mixture
     return (H == 256 and 1 <= M <= 32) or (H == 512 and 1 <= M <= 20)
+
+
+def fused_vae_ln_ok(model) -> bool:
+    """A :class:`SketchVAE` with a ``layer_norm`` decoder that
+    ``csrc/decode_vae_ln.hip`` takes: the sizes and mixture counts of
+    :func:`fused_vae_ok`."""
+    from ..models.vae import SketchVAE
+    if not isinstance(model, SketchVAE) or model.cfg.dec_model != "layer_norm":
+        return False
+    H, M = model.cfg.dec_rnn_size, model.cfg.num_mixture
+    return (H == 256 and 1 <= M <= 32) or (H == 512 and 1 <= M <= 20)
+
+
+def fused_vae_kind(model) -> Optional[str]:
+    """``"lstm"`` / ``"layer_norm"``: which whole-sketch kernel decodes
+    ``model`` (:func:`fused_vae_decoder`); None if neither does."""
+    if fused_vae_ok(model):
+        return "lstm"
+    if fused_vae_ln_ok(model):
+        return "layer_norm"
+    return None
 
 
 def _chunk_rows(L: int, mtw: int, cus: int = 256, H: int = _H) -> int:
@@ -207,27 +238,26 @@ class FusedRefDecoder:
         return z
 
 
-class FusedVAEDecoder:
-    """B sketches of N strokes from a :class:`SketchVAE` with a plain ``lstm``
-    decoder (``csrc/decode_vae.hip``): the LSTM layer, the MDN head and the
-    sampler of every step of ``chunk`` steps in one launch per chunk of rows.
+class _FusedVAEBase:
+    """Host side of the whole-sketch VAE decoders: the latent, the buffers,
+    the chunked launch loop with the all-done exit, prefixes. A subclass
+    names its kernel: ``_eligible`` / ``_NEEDS``, ``_cell_weights``, ``_row_term``
+    (the per-row fp32 gate term), ``_FLAGS`` (flag words per row block),
+    ``_extra`` (per-launch-chunk buffers of its own) and ``_launch``."""
 
-    Semantics are those of ``GraphDecoder`` in VAE mode (start token
-    ``[0, 0, 1, 0, 0]``, identical hash random numbers, temperature on
-    mixture, pen and sigma, end-of-sketch padding of finished rows), with
-    bf16 MFMA operands and fp32 state. After each chunk of steps the host
-    reads whether every row has ended; if so the remaining chunks are not
-    launched and their strokes are filled with padding (``steps_run`` records
-    the steps executed). Chunking does not change a single bit of the result.
-    ``layer_norm`` and ``hyper`` decoders are not eligible
-    (:func:`fused_vae_ok`); they keep using ``GraphDecoder``.
-    """
+    _NEEDS = ""
+    _FLAGS = _FLAG_STRIDE
+
+    @staticmethod
+    def _eligible(model) -> bool:
+        raise NotImplementedError
 
     def __init__(self, model, batch: int, steps: int, temperature: float = 1.0, greedy: bool = False,
                  chunk: int = 50, early_exit: bool = True):
-        if not fused_vae_ok(model):
-            raise ValueError("FusedVAEDecoder: needs a SketchVAE with an lstm decoder of size 256 (M <= 32) "
-                             "or 512 (M <= 20)")
+        self._name = type(self).__name__
+        if not self._eligible(model):
+            raise ValueError("%s: needs a SketchVAE with %s decoder of size 256 (M <= 32) or 512 (M <= 20)"
+                             % (self._name, self._NEEDS))
         self.lib = native.require_hip()
         self.model = model
         self.B, self.N = int(batch), int(steps)
@@ -240,8 +270,8 @@ class FusedVAEDecoder:
         cus = torch.cuda.get_device_properties(self.dev).multi_processor_count if self.dev.type == "cuda" else 256
         self.rows = _chunk_rows(1, 1 if self.B <= 16 else 2, cus, self.H)
         if self.rows <= 0:
-            raise NotCoResident("FusedVAEDecoder: %d CUs cannot hold one row block (%d workgroups)"
-                                % (cus, self.H // 16 + 1))
+            raise NotCoResident("%s: %d CUs cannot hold one row block (%d workgroups)"
+                                % (self._name, cus, self.H // 16 + 1))
         c = max(int(chunk), 1)
         self.ranges = [(t, min(t + c, self.N)) for t in range(0, self.N, c)]
         self.early_exit = bool(early_exit)
@@ -264,10 +294,10 @@ class FusedVAEDecoder:
             "WT": p.W_h.detach().t().to(bf).contiguous(),            # [4H, H]
             "Wx": Wx[:5].contiguous(),                               # [5, 4H] stroke rows
             "Wz": Wx[5:].contiguous(),                               # [z_in, 4H] rows of the conditioning
-            "b": p.bias.detach().float().contiguous(),
             "WoT": WoT,
             "bo": m.output_b.detach().float().contiguous(),
         }
+        self._w.update(self._cell_weights(p))
         self._sig = sig
         return self._w
 
@@ -291,9 +321,8 @@ class FusedVAEDecoder:
         w = self._weights()
         B, N, H, dev, f32 = self.B, self.N, self.H, self.dev, torch.float32
         zc, (h0, c0) = self._latent(seed, z, labels)
-        zb = (zc.to(f32) @ w["Wz"] + w["b"]) if zc is not None else w["b"].expand(B, 4 * H)
         st = {
-            "zb": zb.contiguous(), "c": c0.to(f32).contiguous().clone(),
+            "zb": self._row_term(zc, w).contiguous(), "c": c0.to(f32).contiguous().clone(),
             "out": torch.empty(B, N, 5, dtype=f32, device=dev),
             "done": torch.zeros(B, dtype=torch.int32, device=dev),
             "nforced": nforced.to(dev, torch.int32).contiguous() if nforced is not None else None,
@@ -306,25 +335,42 @@ class FusedVAEDecoder:
             nrb = -(-Bc // (16 * mtw))
             hbuf = torch.empty(N + 1, Bc, H, dtype=torch.bfloat16, device=dev)
             hbuf[0] = h0[r0:r0 + Bc]
-            st["chunks"].append({
+            if self._poison():
+                hbuf[1:] = float("nan")
+            ch = self._extra(nrb, mtw)
+            ch.update({
                 "r0": r0, "Bc": Bc, "mtw": mtw, "nrb": nrb, "hbuf": hbuf,
                 "xin": xin[:, r0:r0 + Bc].contiguous(),
                 "zout": torch.zeros(N, Bc, self.nout, dtype=f32, device=dev) if want_z else None,
-                "flags": torch.empty(nrb * _FLAG_STRIDE, dtype=torch.int32, device=dev),   # zeroed by the launcher
+                "flags": torch.empty(nrb * self._FLAGS, dtype=torch.int32, device=dev),   # zeroed by the launcher
             })
+            st["chunks"].append(ch)
         return st
 
-    def _launch(self, st, ch, t0: int, t1: int):
-        from ..ops._hipapi import DecVaeArgs
+    # -- what a subclass supplies ---------------------------------------------------------
+    def _cell_weights(self, p) -> dict:
+        """fp32 parameters of the cell beyond W_x / W_h (bias or layer norms)."""
+        raise NotImplementedError
+
+    def _row_term(self, zc, w) -> torch.Tensor:
+        """``[B, 4H]`` fp32 term the kernel adds to every step's gates of a row."""
+        raise NotImplementedError
+
+    def _poison(self) -> bool:
+        return False
+
+    def _extra(self, nrb: int, mtw: int) -> dict:
+        return {}
+
+    def _fill_common(self, a, st, ch, t0: int, t1: int):
+        """The fields both kernels' argument structs name alike."""
         from ..ops.recurrent import cluster_error_flag
         w = self._weights()
         r0, Bc = ch["r0"], ch["Bc"]
-        a = DecVaeArgs()
         a.N, a.B, a.H, a.mtw, a.nrb = self.N, Bc, self.H, ch["mtw"], ch["nrb"]
         a.M, a.nout, a.noutp, a.greedy, a.row0 = self.M, self.nout, self.noutp, int(self.greedy), int(r0)
         a.t0, a.t1, a.temp, a.forget_bias = int(t0), int(t1), self.temp, 1.0
         a.WT, a.Wx, a.WoT, a.bo = w["WT"].data_ptr(), w["Wx"].data_ptr(), w["WoT"].data_ptr(), w["bo"].data_ptr()
-        a.zb = st["zb"][r0:].data_ptr()
         a.c0 = a.cT = st["c"][r0:].data_ptr()
         a.hbuf, a.xin = ch["hbuf"].data_ptr(), ch["xin"].data_ptr()
         a.out, a.done = st["out"][r0:].data_ptr(), st["done"][r0:].data_ptr()
@@ -332,11 +378,17 @@ class FusedVAEDecoder:
         a.zout = ch["zout"].data_ptr() if ch["zout"] is not None else None
         a.seed, a.flags = self.seed.data_ptr(), ch["flags"].data_ptr()
         a.err = cluster_error_flag(self.dev).data_ptr()
-        rc = self.lib.lib.skr_decode_vae(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        return w
+
+    def _call(self, fn, name: str, a):
+        rc = fn(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         if rc == -8:
-            raise NotCoResident("skr_decode_vae: workgroups cannot be co-resident on this device (code -8)")
+            raise NotCoResident("%s: workgroups cannot be co-resident on this device (code -8)" % name)
         if rc != 0:
-            raise RuntimeError("skr_decode_vae: launch failed (code %d)" % rc)
+            raise RuntimeError("%s: launch failed (code %d)" % (name, rc))
+
+    def _launch(self, st, ch, t0: int, t1: int):
+        raise NotImplementedError
 
     @torch.no_grad()
     def run(self, seed: int = 0, z: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
@@ -361,15 +413,20 @@ class FusedVAEDecoder:
             plen = (torch.full((B,), P, dtype=torch.int64, device=dev) if prefix_len is None
                     else torch.as_tensor(prefix_len).to(dev, torch.int64))
             if prefix.shape[0] != B or prefix.shape[2] != 5 or plen.shape != (B,):
-                raise ValueError("FusedVAEDecoder.run: prefix must be [B, P, 5] and prefix_len [B]")
+                raise ValueError(self._name + ".run: prefix must be [B, P, 5] and prefix_len [B]")
             if bool((plen < 0).any()) or bool((plen > min(P, N)).any()):
-                raise ValueError("FusedVAEDecoder.run: prefix_len must lie in [0, min(P, steps)]")
+                raise ValueError(self._name + ".run: prefix_len must lie in [0, min(P, steps)]")
             inside = torch.arange(P, device=dev)[None, :] < plen[:, None]
             if bool((inside & (prefix[:, :, 4] > 0)).any()):
-                raise ValueError("FusedVAEDecoder.run: a prefix ends its sketch (pen state 4) inside its length")
+                raise ValueError(self._name + ".run: a prefix ends its sketch (pen state 4) inside its length")
             Pn = min(P, N)
             xin[1:Pn + 1, :, :5] = (prefix[:, :Pn] * inside[:, :Pn, None]).transpose(0, 1)
             nforced = plen
+        if self._poison():            # rows of xin[1:] no prefix supplies: the head must write them first
+            free = torch.ones(N, B, dtype=torch.bool, device=dev)
+            if nforced is not None:
+                free = torch.arange(1, N + 1, device=dev)[:, None] > nforced[None, :]
+            xin[1:][free] = float("nan")
         st = self._begin(seed, z, labels, xin, nforced, return_z)
         ran = N
         for t0, t1 in self.ranges:
@@ -409,3 +466,155 @@ class FusedVAEDecoder:
             self._launch(st, ch, 0, N)
         check_cluster_errors(self.dev)
         return torch.cat([ch["zout"] for ch in st["chunks"]], 1)
+
+
+class FusedVAEDecoder(_FusedVAEBase):
+    """B sketches of N strokes from a :class:`SketchVAE` with a plain ``lstm``
+    decoder (``csrc/decode_vae.hip``): the LSTM layer, the MDN head and the
+    sampler of every step of ``chunk`` steps in one launch per chunk of rows.
+
+    Semantics are those of ``GraphDecoder`` in VAE mode (start token
+    ``[0, 0, 1, 0, 0]``, identical hash random numbers, temperature on
+    mixture, pen and sigma, end-of-sketch padding of finished rows), with
+    bf16 MFMA operands and fp32 state. After each chunk of steps the host
+    reads whether every row has ended; if so the remaining chunks are not
+    launched and their strokes are filled with padding (``steps_run`` records
+    the steps executed). Chunking does not change a single bit of the result.
+    ``layer_norm`` decoders are :class:`FusedLNVAEDecoder`'s
+    (:func:`fused_vae_decoder` picks); ``hyper`` decoders are not eligible
+    and keep using ``GraphDecoder``.
+    """
+
+    _NEEDS = "an lstm"
+    _eligible = staticmethod(fused_vae_ok)
+
+    def _cell_weights(self, p):
+        return {"b": p.bias.detach().float().contiguous()}
+
+    def _row_term(self, zc, w):
+        """``zb [B, 4H] = zc @ W_x[5:] + bias``."""
+        if zc is None:
+            return w["b"].expand(self.B, 4 * self.H)
+        return zc.to(torch.float32) @ w["Wz"] + w["b"]
+
+    def _launch(self, st, ch, t0: int, t1: int):
+        from ..ops._hipapi import DecVaeArgs
+        a = DecVaeArgs()
+        self._fill_common(a, st, ch, t0, t1)
+        a.zb = st["zb"][ch["r0"]:].data_ptr()
+        self._call(self.lib.lib.skr_decode_vae, "skr_decode_vae", a)
+
+
+class FusedLNVAEDecoder(_FusedVAEBase):
+    """:class:`FusedVAEDecoder` for a ``layer_norm`` decoder
+    (``csrc/decode_vae_ln.hip``): same surface, same semantics, same host
+    loop. Per step the ``H/16`` layer workgroups of a row block exchange the
+    per-row partial statistics of the two layer norms (gates, then the new
+    cell) inside the launch; :func:`ln_decode_step_transcription` is the
+    kernel's arithmetic in PyTorch. With the module attribute
+    ``LN_DECODE_POISON`` set, every buffer workgroups hand to each other inside
+    a launch (statistics slots, ``hbuf[1:]``, the rows of ``xin[1:]`` no
+    prefix supplies) is NaN-filled before each run, so a read that precedes
+    its write shows in the output."""
+
+    _NEEDS = "a layer_norm"
+    _FLAGS = _LN_FLAG_STRIDE
+    _eligible = staticmethod(fused_vae_ln_ok)
+
+    def _cell_weights(self, p):
+        return {k: getattr(p, k).detach().float().contiguous()
+                for k in ("ln_gamma", "ln_beta", "lnc_gamma", "lnc_beta")}
+
+    def _row_term(self, zc, w):
+        """``zp [B, 4H] = zc @ W_x[5:]`` (LNLSTMParams has no bias)."""
+        if zc is None:
+            return torch.zeros(self.B, 4 * self.H, device=self.dev)
+        return zc.to(torch.float32) @ w["Wz"]
+
+    def _poison(self) -> bool:
+        return bool(LN_DECODE_POISON)
+
+    def _extra(self, nrb: int, mtw: int) -> dict:
+        # [parity][row block][workgroup][row][gate][mean, M2] and [...][row][mean, M2]
+        n = 2 * nrb * (self.H // 16) * 16 * mtw
+        fill = float("nan") if self._poison() else 0.0
+        return {"gstat": torch.full((n * 8,), fill, device=self.dev),
+                "cstat": torch.full((n * 2,), fill, device=self.dev)}
+
+    def _launch(self, st, ch, t0: int, t1: int):
+        from ..ops._hipapi import DecVaeLnArgs
+        a = DecVaeLnArgs()
+        w = self._fill_common(a, st, ch, t0, t1)
+        a.zp = st["zb"][ch["r0"]:].data_ptr()
+        a.ln_g, a.ln_b = w["ln_gamma"].data_ptr(), w["ln_beta"].data_ptr()
+        a.lnc_g, a.lnc_b = w["lnc_gamma"].data_ptr(), w["lnc_beta"].data_ptr()
+        a.gstat, a.cstat = ch["gstat"].data_ptr(), ch["cstat"].data_ptr()
+        self._call(self.lib.lib.skr_decode_vae_ln, "skr_decode_vae_ln", a)
+
+
+def fused_vae_decoder(model, batch: int, steps: int, temperature: float = 1.0, greedy: bool = False,
+                      chunk: int = 50, early_exit: bool = True):
+    """The whole-sketch decoder that takes ``model``: :class:`FusedVAEDecoder`
+    (plain ``lstm``) or :class:`FusedLNVAEDecoder` (``layer_norm``);
+    ``ValueError`` for every other model (:func:`fused_vae_kind` is None)."""
+    kind = fused_vae_kind(model)
+    if kind is None:
+        raise ValueError("fused_vae_decoder: needs a SketchVAE with an lstm or layer_norm decoder of size 256 "
+                         "(M <= 32) or 512 (M <= 20)")
+    cls = FusedVAEDecoder if kind == "lstm" else FusedLNVAEDecoder
+    return cls(model, batch, steps, temperature, greedy, chunk, early_exit)
+
+
+@torch.no_grad()
+def ln_decode_step_transcription(model, x: torch.Tensor, zp: Optional[torch.Tensor], h: torch.Tensor,
+                                 c: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """One step of ``csrc/decode_vae_ln.hip`` in PyTorch, in the form the
+    kernel computes it (the direct form: statistics of the complete gate
+    pre-activations, exchanged after the stroke is known).
+
+    ``x [B, 5]`` the fed stroke, ``zp [B, 4H] = zc @ W_x[5:]`` (None: no z
+    input), ``h [B, H]`` the carried h **already rounded to bf16** (held as
+    fp32), ``c [B, H]`` fp32. Returns ``(z [B, 3+6M], h', c')`` with ``h'``
+    rounded to bf16 again, as the kernel stores it.
+
+    What it models: W_h, W_out and the carried h in bf16 with fp32
+    accumulation; the stroke and z terms in fp32; per block of 16 units a
+    ``(mean_k, M2_k)`` partial, combined over the ``H/16`` blocks in block
+    order as ``mean = sum mean_k / NW``, ``M2 = sum M2_k + 16 sum (mean_k -
+    mean)^2``, ``rstd = rsqrt(M2 / H + 1e-3)``; the un-normalised fp32 ``c'``
+    carried. What it does not: the MFMA's accumulation order and the
+    device's exp / reciprocal -- the factor 2 in the GPU test's bound."""
+    p, H, f32, bf = model.dec, model.cfg.dec_rnn_size, torch.float32, torch.bfloat16
+    NW = H // 16
+
+    def stats(v):                       # v [..., H] -> mean, rstd [..., 1]
+        blk = v.reshape(*v.shape[:-1], NW, 16)
+        mk = blk.sum(-1) * (1.0 / 16)
+        qk = ((blk - mk[..., None]) ** 2).sum(-1)
+        sm, sq = torch.zeros_like(mk[..., 0]), torch.zeros_like(mk[..., 0])
+        for k in range(NW):             # block order
+            sm = sm + mk[..., k]
+            sq = sq + qk[..., k]
+        mean = sm * (1.0 / NW)
+        sd = torch.zeros_like(mean)
+        for k in range(NW):
+            sd = sd + (mk[..., k] - mean) ** 2
+        rstd = torch.rsqrt((sq + 16.0 * sd) * (1.0 / H) + 1e-3)
+        return mean[..., None], rstd[..., None]
+
+    Wh = p.W_h.detach().to(bf).to(f32)
+    Wx = p.W_x.detach().to(f32)
+    g = h.to(f32) @ Wh + x.to(f32) @ Wx[:5]
+    if zp is not None:
+        g = g + zp
+    B = g.shape[0]
+    g4 = g.reshape(B, 4, H)
+    mean, rstd = stats(g4)
+    gn = (g4 - mean) * rstd * p.ln_gamma.detach().to(f32).reshape(4, H) + p.ln_beta.detach().to(f32).reshape(4, H)
+    i, j, f, o = gn.unbind(1)
+    c2 = c * torch.sigmoid(f + 1.0) + torch.sigmoid(i) * torch.tanh(j)
+    mean, rstd = stats(c2)
+    h2 = torch.tanh(p.lnc_gamma.detach().to(f32) * (c2 - mean) * rstd + p.lnc_beta.detach().to(f32)) * torch.sigmoid(o)
+    h2 = h2.to(bf).to(f32)
+    z = h2 @ model.output_w.detach().to(bf).to(f32) + model.output_b.detach().to(f32)
+    return z, h2, c2

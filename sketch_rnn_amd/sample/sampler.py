@@ -20,8 +20,8 @@ replayed; finished rows emit end-of-sketch padding. No host round trip per
 stroke (the reference does two ``sess.run`` transfers per stroke). HyperLSTM
 decoders step through :class:`~.hyper_step.HyperStepDecoder` (state in
 place, seven hand-written kernels per stroke); the reference model and
-the VAE's plain ``lstm`` decoders have whole-sketch decoders in
-:mod:`.fused` (the VAE one is opt-in: ``vae_sample --fused``).
+the VAE's plain ``lstm`` and ``layer_norm`` decoders have whole-sketch
+decoders in :mod:`.fused` (the VAE ones are opt-in: ``vae_sample --fused``).
 """
 from __future__ import annotations
 
