@@ -274,6 +274,87 @@ class SketchVAE(nn.Module):
             out["_enc"] = enc_cut
         return out
 
+    # -- per-sketch likelihood -----------------------------------------------------------------
+    @torch.no_grad()
+    def score(self, strokes: torch.Tensor, lengths: torch.Tensor, labels: Optional[torch.Tensor] = None, *,
+              samples: int = 0, seed: int = 0, eps: Optional[torch.Tensor] = None,
+              include_end: Optional[bool] = None, max_len: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """Per-sketch negative log-likelihood terms, each ``[B]``, without
+        dropout (``ops.mdn_head_score``): ``shape`` and ``pen`` summed over a
+        sketch's own points, ``nll = shape + pen`` and ``points``, the
+        positions counted. ``include_end`` also counts the pen term of the
+        row after the last point (the model's probability of ending the
+        sketch there), one more position for every sketch shorter than Nmax.
+
+        ``samples == 0``: the decoder is conditioned on ``z = mu`` (nothing
+        for an unconditional model); ``include_end`` defaults to False, so
+        ``nll.sum() / (Nmax * B)`` is ``loss(train=False)["r_cost"]`` of an
+        evaluation-mode model at the same ``z``.
+
+        ``samples = K >= 1`` (conditional models): one decoder pass per
+        ``z_k = mu + exp(presig / 2) eps_k`` with ``eps [K, B, z_size]`` as
+        given, or the stateless hash noise of ``(seed, k)``. With
+        ``log w_k = -nll_k + log p(z_k) - log q(z_k | x)`` (densities summed
+        over the z dimensions) it adds ``elbo = mean_k log w_k``,
+        ``iwae = logsumexp_k log w_k - log K`` and the analytic ``kl`` summed
+        over dimensions; ``shape``, ``pen`` and ``nll`` are means over ``k``
+        and ``include_end`` defaults to True (a likelihood counts the end).
+
+        ``max_len`` (host int, e.g. the batch's largest length): only the
+        steps that can be counted are encoded, decoded and scored -- exact,
+        the recurrences are causal and later rows are masked."""
+        import math
+        cfg = self.cfg
+        B, Nmax = strokes.shape[0], strokes.shape[1] - 1
+        dev = strokes.device
+        if eps is not None and samples == 0:
+            samples = int(eps.shape[0])
+        K = int(samples)
+        if K < 0:
+            raise ValueError("samples must be >= 0")
+        if K >= 1 and not cfg.conditional:
+            raise ValueError("score(samples >= 1) needs a conditional model: an unconditional one has no z to sample")
+        if eps is not None and tuple(eps.shape) != (K, B, cfg.z_size):
+            raise ValueError("eps must be [samples, B, z_size]")
+        if include_end is None:
+            include_end = K >= 1
+        Te = Nmax if max_len is None else max(1, min(Nmax, int(max_len)))   # steps the encoder can read
+        T = min(Nmax, Te + 1) if include_end else Te                         # steps that can be counted
+        sT = strokes.transpose(0, 1).contiguous()
+        labels = labels if cfg.num_classes > 0 else None
+        lens = lengths.to(torch.int64)
+        points = lens.clamp(0, T)
+        if include_end:
+            points = points + (lens < T).to(torch.int64)
+        target = sT[1:T + 1]
+
+        def one(z):
+            zc = self.condition(z, labels, B, dev)
+            out, _ = self.decode(sT[:T], zc, self.initial_state(zc, B, dev), train=False, seed=0)
+            return ops.mdn_head_score(out, self.output_w, self.output_b, target, lens, cfg.num_mixture,
+                                      include_end=include_end, x_lp=getattr(out, "_skr_lp", None))
+
+        if K == 0:
+            z = self.encoder(sT[1:Te + 1], lengths, False, 0)[0] if cfg.conditional else None
+            shape, pen = one(z)
+            return {"shape": shape, "pen": pen, "nll": shape + pen, "points": points}
+        mu, presig = self.encoder(sT[1:Te + 1], lengths, False, 0)
+        sigma = torch.exp(presig / 2.0)
+        shapes, pens, logw = [], [], []
+        for k in range(K):
+            e = eps[k].to(mu.dtype) if eps is not None else C.hash_normal(seed, _S_EPS, k, (B, cfg.z_size), dev)
+            z = mu + sigma * e
+            shape, pen = one(z)
+            log_p = -0.5 * (z * z + math.log(2.0 * math.pi)).sum(-1)
+            log_q = -0.5 * (e * e + presig + math.log(2.0 * math.pi)).sum(-1)
+            shapes.append(shape)
+            pens.append(pen)
+            logw.append(-(shape + pen) + log_p - log_q)
+        shape, pen, logw = torch.stack(shapes).mean(0), torch.stack(pens).mean(0), torch.stack(logw)
+        return {"shape": shape, "pen": pen, "nll": shape + pen, "points": points,
+                "elbo": logw.mean(0), "iwae": torch.logsumexp(logw, 0) - math.log(K),
+                "kl": -0.5 * (1 + presig - mu * mu - torch.exp(presig)).sum(-1)}
+
     # -- sampling helpers --------------------------------------------------------------------
     @torch.no_grad()
     def decode_step(self, x: torch.Tensor, zc: Optional[torch.Tensor], state):

@@ -163,3 +163,26 @@ def mdn_head_loss(x, W, b, target, M: int, mode: str = "magenta", stroke_importa
         x2 = x2 * dropout_mask(drop_seed, drop_stream, 0, x2.shape, drop_keep, x2.device)
     z = gemm.linear(x2, W, b)
     return mdn_loss(z, target, M, mode, stroke_importance, is_training, clamp, eps)
+
+
+def mdn_head_score(x, W, b, target, lengths, M: int, include_end: bool = False, eps: float = 1e-6, x_lp=None):
+    """Per-sketch likelihood scores ``(shape [B], pen [B])`` of the head
+    ``z = x @ W + b`` (Magenta mode): ``x [T, B, Hd]`` time-major decoder
+    outputs, ``target [T, B, 5]``, ``lengths [B]``. The per-row terms are
+    those of ``mdn_loss_torch(mode="magenta", is_training=False)`` before
+    its mask and mean, summed over ``t < lengths[b]``; ``include_end`` adds
+    the pen term of row ``lengths[b]`` (the end-of-sketch row) when it
+    exists. Rows past a sketch's counted positions contribute exactly zero.
+
+    bf16 HIP compute: one kernel (csrc/mdn_score.hip) projects on MFMA and
+    sums per sketch without writing ``z`` or touching padded rows; ``x_lp``
+    is an optional bf16 copy of ``x`` it reads instead. Otherwise the same
+    definition in PyTorch. No autograd."""
+    if torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in (x, W, b, target)):
+        raise RuntimeError("mdn_head_score has no gradient: call it under torch.no_grad() or detach its inputs")
+    if target.dim() != 3 or target.shape[-1] != 5 or x.numel() != target.shape[0] * target.shape[1] * W.shape[0]:
+        raise ValueError("mdn_head_score: x [T, B, Hd] and target [T, B, 5] expected")
+    from .mdn_score import mdn_head_score_hip, mdn_head_score_torch, score_fused_ok
+    if score_fused_ok(x, W, M):
+        return mdn_head_score_hip(x, W, b, target, lengths, M, include_end, eps, x_lp)
+    return mdn_head_score_torch(x, W, b, target, lengths, M, include_end, eps)

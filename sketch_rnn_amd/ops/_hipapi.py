@@ -236,6 +236,17 @@ class HeadDw(C.Structure):
     ]
 
 
+class HeadScore(C.Structure):
+    """Mirror of ``HeadScore`` in csrc/mdn_score.hip (per-sketch MDN head scores)."""
+    _fields_ = [
+        ("X", _p), ("ldx", _i64), ("Hd", _i), ("x_bf16", _i),
+        ("Wt", _p), ("bias", _p), ("tgt", _p), ("ldt", _i64), ("lengths", _p),
+        ("T", _i), ("B", _i), ("M", _i), ("NOUT", _i), ("NOUTP", _i), ("include_end", _i),
+        ("tps", _i), ("S", _i), ("log_floor", _f),
+        ("part", _p), ("score", _p),
+    ]
+
+
 class DecLayer(C.Structure):
     """Mirror of ``DecLayer`` in csrc/decode_ref.hip (fused whole-sketch decoder)."""
     _fields_ = [
@@ -486,6 +497,8 @@ class HipLib:
         lib.skr_mdn_head_dx.restype = _i
         lib.skr_mdn_head_dw.argtypes = [C.POINTER(HeadDw), _i, _i, _p, _p, _p]
         lib.skr_mdn_head_dw.restype = _i
+        lib.skr_mdn_head_score.argtypes = [C.POINTER(HeadScore), _p]
+        lib.skr_mdn_head_score.restype = _i
         lib.skr_hyper_mod_fwd.argtypes = [_p, _i64, _p, _p, _p, _p, _i64, _i, _p, _p, _p, _p, _i, _i, _i,
                                           C.POINTER(ModDecode), _p]
         lib.skr_hyper_mod_fwd.restype = _i
@@ -516,6 +529,7 @@ class HipLib:
                           ("skr_mdn_head_fwd_args_size", HeadFwd),
                           ("skr_mdn_head_dx_args_size", HeadDx),
                           ("skr_mdn_head_dw_args_size", HeadDw),
+                          ("skr_mdn_head_score_args_size", HeadScore),
                           ("skr_decode_ref_args_size", DecArgs),
                           ("skr_decode_vae_args_size", DecVaeArgs),
                           ("skr_decode_vae_ln_args_size", DecVaeLnArgs),

@@ -448,6 +448,30 @@ class VAETrainer:
         res = {k: v / max(n, 1) for k, v in tot.items()}
         return dp.average_scalars(res)
 
+    @torch.no_grad()
+    def evaluate_sketches(self, dataset, max_batches: Optional[int] = None, samples: int = 0,
+                          seed: int = 1234) -> Dict[str, np.ndarray]:
+        """Per-sketch scores (``SketchVAE.score``) concatenated over the
+        dataset's batches in order: ``shape``, ``pen``, ``nll``, ``points``
+        and, with ``samples >= 1``, ``elbo``, ``iwae``, ``kl``. Each batch is
+        decoded only up to its own longest sketch (the dataset is sorted by
+        length) and comes back in one device-to-host copy. Batch ``b`` draws
+        its noise from ``seed + b`` (stateless: two models scored with the
+        same seed see the same noise)."""
+        n = dataset.num_batches if max_batches is None else min(max_batches, dataset.num_batches)
+        keys, rows = None, []
+        for b in range(n):
+            batch = dataset.get_batch(b)
+            s, l, c = self.batch_to_device(batch)
+            out = self.model.score(s, l, c if self.cfg.num_classes > 0 else None, samples=samples, seed=seed + b,
+                                   max_len=int(np.max(batch[1])))
+            keys = keys or list(out)
+            rows.append(torch.stack([out[k].to(torch.float64) for k in keys]).cpu().numpy())
+        if not rows:
+            return {}
+        cat = np.concatenate(rows, 1)
+        return {k: (cat[i].astype(np.int64) if k == "points" else cat[i]) for i, k in enumerate(keys)}
+
     def save(self):
         if self.rank != 0:
             return None
