@@ -301,7 +301,7 @@ __device__ __forceinline__ void stb_sc1(void* p, const float (&v)[V]) {
 // [c H / CL, (c + 1) H / CL), NT V == H / CL), and its two LayerNorm-backward
 // row sums are exchanged between them in-launch as tagged granules
 // (cluster_allgather, csrc/cell_fwd_body.h; a.part / a.err, tag = step + 1).
-template <int NT, int V, bool MOD, int DO, bool CHAIN = false, bool DVSC1 = false, int POLL = 1, int CL = 1>
+template <int NT, int V, bool MOD, int DO, bool CHAIN = false, bool DVSC1 = false, int CL = 1>
 __device__ __forceinline__ void row_bwd_body(const BwdArgs& a, const int b, const uint32_t* chain_cnt = nullptr,
                                              uint32_t chain_target = 0, int* chain_err = nullptr, const int c = 0) {
     static_assert(!CHAIN || V == 4, "chained row: 16-byte slab loads");
@@ -348,7 +348,7 @@ __device__ __forceinline__ void row_bwd_body(const BwdArgs& a, const int b, cons
         }
     }
     if constexpr (CHAIN) {
-        chain_wait<POLL>(chain_cnt, chain_target, chain_err);
+        chain_wait<1>(chain_cnt, chain_target, chain_err);
         if (n1) {
             const __amdgpu_buffer_rsrc_t r = rsrc(a.dh_rec, 0x7fffffff);
             const int64_t base = (int64_t)b * a.ld_dh_rec + u0;

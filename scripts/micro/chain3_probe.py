@@ -71,15 +71,12 @@ def main():
             out, _ = ops.hyper_sequence(p, x, *st, drop_keep=0.9, drop_seed=1, drop_stream=9, zc=z)
             torch.autograd.grad((out * w).sum(), [z] + list(p.parameters()))
         f_ms = timed(fwd, 5)
-        for var, c3, probe, poll in (("chain2", False, 0, 1), ("chain2_poll4", False, 0, 4),
-                                     ("chain2_poll16", False, 0, 16), ("chain3", True, 0, 1),
-                                     ("probe1", True, 1, 1), ("probe2", True, 2, 1), ("probe3", True, 3, 1)):
+        for var, c3, probe in (("chain2", False, 0), ("chain3", True, 0), ("probe1", True, 1), ("probe2", True, 2),
+                               ("probe3", True, 3)):
             hyper.CHAIN3 = c3
             lib.skr_chain3_set_probe(probe)
-            lib.skr_chain_set_poll(poll)
             fb = timed(fwdbwd, 5)
             lib.skr_chain3_set_probe(0)
-            lib.skr_chain_set_poll(1)
             print(json.dumps({"B": B, "T": T, "variant": var, "fwd_ms": round(f_ms, 3), "fwdbwd_ms": round(fb, 3),
                               "bwd_us_per_step": round(1000 * (fb - f_ms) / T, 2)}), flush=True)
     hyper.CHAIN3 = True

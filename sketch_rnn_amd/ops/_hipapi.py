@@ -403,8 +403,6 @@ class HipLib:
         lib.skr_bproj_fwd.restype = _i
         lib.skr_bproj_bwd.argtypes = [_p, _p, _i, _i64, _p, _p, _i, _i, _i, _i, _p]
         lib.skr_bproj_bwd.restype = _i
-        lib.skr_skew_ln_fwd.argtypes = [C.POINTER(LstmFwdArgs), _p, _p, C.POINTER(ChainSync), _p]
-        lib.skr_skew_ln_fwd.restype = _i
         lib.skr_chain_ln_set_probe.argtypes = [_i]
         lib.skr_chain_ln_set_probe.restype = _i
         lib.skr_hyper_mod_set_probe.argtypes = [_i]
@@ -453,8 +451,6 @@ class HipLib:
         lib.skr_cell_set_oversub.restype = _i
         lib.skr_hyper_mod_set_zgrid.argtypes = [_i]
         lib.skr_hyper_mod_set_zgrid.restype = _i
-        lib.skr_gemm_set_ra.argtypes = [_i]
-        lib.skr_gemm_set_ra.restype = _i
         lib.skr_chain_ln_fwd.argtypes = [C.POINTER(GemmProblem), _i, C.POINTER(LstmFwdArgs), C.POINTER(ChainSync), _p]
         lib.skr_chain_ln_fwd.restype = _i
         lib.skr_chain_ln_bwd.argtypes = [C.POINTER(GemmProblem), _i, C.POINTER(LstmBwdArgs), C.POINTER(ChainSync), _p]
@@ -471,8 +467,6 @@ class HipLib:
         lib.skr_mx8_gemm.restype = _i
         lib.skr_mx8_set_layout.argtypes = [_i]
         lib.skr_mx8_set_layout.restype = _i
-        lib.skr_chain_set_poll.argtypes = [_i]
-        lib.skr_chain_set_poll.restype = _i
         lib.skr_chain3_set_probe.argtypes = [_i]
         lib.skr_chain3_set_probe.restype = _i
         lib.skr_lstm_fused_fwd.argtypes = [C.POINTER(FusedFwdArgs), _p]
