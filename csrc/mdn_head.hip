@@ -383,7 +383,11 @@ __global__ __launch_bounds__(256) void mdn_head_dx(const HeadDx a) {
         *(u32x4*)(Ws + n * ldw + c * 8) = *(const u32x4*)(a.Wb + (int64_t)(col0 + n) * NOUTP + c * 8);
     }
     __syncthreads();
+    // The upstream scales multiply fp32 sums, never the stored bf16 dz (a
+    // second bf16 rounding): the mixture scale the accumulators; the three pen
+    // columns, when their scale differs, as fp32 products after the MFMA.
     const float sp = a.scale[0], sm = a.scale[1];
+    const bool split = sp != sm;
     const int64_t arow = min(row0 + w * 16 + fr, a.N - 1);
     f32x4 acc[kDxCols / 16];
 #pragma unroll
@@ -391,18 +395,9 @@ __global__ __launch_bounds__(256) void mdn_head_dx(const HeadDx a) {
     for (int ks = 0; ks < NOUTP / 32; ++ks) {
         const int k = ks * 32 + fq * 8;
         u32x4 raw = *(const u32x4*)(a.dz + arow * a.ldz + k);
-        if (k < 8) {   // pen columns 0..2 carry the pen scale
-            bf16x8 v = __builtin_bit_cast(bf16x8, raw);
-            float f[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) f[j] = (float)v[j] * (k + j < 3 ? sp : sm);
-            raw = u32x4{pack_bf16(f[0], f[1]), pack_bf16(f[2], f[3]), pack_bf16(f[4], f[5]), pack_bf16(f[6], f[7])};
-        } else if (sm != 1.0f) {
-            bf16x8 v = __builtin_bit_cast(bf16x8, raw);
-            float f[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) f[j] = (float)v[j] * sm;
-            raw = u32x4{pack_bf16(f[0], f[1]), pack_bf16(f[2], f[3]), pack_bf16(f[4], f[5]), pack_bf16(f[6], f[7])};
+        if (split && k < 8) {   // pen columns 0..2 (their own scale) are added after the MFMA
+            raw[0] = 0u;
+            raw[1] &= 0xffff0000u;
         }
         const bf16x8 A = __builtin_bit_cast(bf16x8, raw);
 #pragma unroll
@@ -416,7 +411,8 @@ __global__ __launch_bounds__(256) void mdn_head_dx(const HeadDx a) {
 #pragma unroll
     for (int c = 0; c < kDxCols / 16; ++c)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) ow[(4 * fq + e) * (kDxCols + 4) + c * 16 + fr] = acc[c][e];
+        for (int e = 0; e < 4; ++e)
+            ow[(4 * fq + e) * (kDxCols + 4) + c * 16 + fr] = sm != 1.0f ? acc[c][e] * sm : acc[c][e];
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     const bool keep_on = a.keep < 1.0f;
@@ -428,6 +424,17 @@ __global__ __launch_bounds__(256) void mdn_head_dx(const HeadDx a) {
         const int64_t row = row0 + w * 16 + rr;
         if (row >= a.N) continue;
         f32x4 v = *(const f32x4*)(ow + rr * (kDxCols + 4) + c4);
+        if (split) {
+            const uint2 u = *(const uint2*)(a.dz + row * a.ldz);   // dz columns 0..3 of this row
+            const float d0 = __uint_as_float(u.x << 16), d1 = __uint_as_float(u.x & 0xffff0000u);
+            const float d2 = __uint_as_float(u.y << 16);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const __hip_bfloat16* wr = Ws + (c4 + q) * ldw;
+                v[q] += sp * (d0 * __bfloat162float(wr[0]) + d1 * __bfloat162float(wr[1]) +
+                              d2 * __bfloat162float(wr[2]));
+            }
+        }
         if (keep_on) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) v[q] *= drop_mult(true, key, row * a.Hd + col0 + c4 + q, a.keep);
@@ -503,14 +510,15 @@ __global__ __launch_bounds__(256) void mdn_head_dw(const HeadDw a) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) xt[f4 + q][rr] = to_bf16(v[q]);
         }
-        // dz chunk [32 rows][NOUTP] -> gt[col][row] (scaled)
+        // dz chunk [32 rows][NOUTP] -> gt[col][row] (the stored bf16 values; the
+        // upstream scale multiplies the fp32 sums below, one output column each)
         for (int p = tid; p < kRC * (NOUTP / 8); p += 256) {
             const int rr = p / (NOUTP / 8), c8 = (p - rr * (NOUTP / 8)) * 8;
             const int64_t row = r0 + rr;
             bf16x8 v = {};
             if (row < r_end) v = __builtin_bit_cast(bf16x8, *(const u32x4*)(a.dz + row * a.ldz + c8));
 #pragma unroll
-            for (int j = 0; j < 8; ++j) gt[c8 + j][rr] = to_bf16((float)v[j] * (c8 + j < 3 ? sp : sm));
+            for (int j = 0; j < 8; ++j) gt[c8 + j][rr] = to_bf16((float)v[j]);
         }
         __syncthreads();
         // wave w: features 16w .. 16w+15 x all output columns, K = 32 rows
@@ -528,8 +536,9 @@ __global__ __launch_bounds__(256) void mdn_head_dw(const HeadDw a) {
 #pragma unroll
     for (int c = 0; c < kMaxNoutP / 16; ++c) {
         if (c < NC) {
+            const float sc = c * 16 + fr < 3 ? sp : sm;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) out[(4 * fq + e) * NOUTP + c * 16 + fr] = acc[c][e];
+            for (int e = 0; e < 4; ++e) out[(4 * fq + e) * NOUTP + c * 16 + fr] = acc[c][e] * sc;
         }
     }
 }

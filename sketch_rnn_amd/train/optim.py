@@ -156,15 +156,17 @@ class FlatAdam:
         sc[5] += skip.float()
         sc[1] += (~skip).float()
         keep = (~skip).float()
+        # a skipped step's gradient is selected to zero BEFORE any product with
+        # the clip scale: NaN * 0 would carry the NaN into m, v and flat
+        g = torch.where(skip, torch.zeros_like(g), g)
         if self.clip_mode == "global_norm":
             scale = self.clip / torch.clamp(norm, min=self.clip)
             sc[3] = scale
-            g = g * torch.where(skip, torch.zeros_like(scale), scale)
+            g = g * torch.where(skip, torch.ones_like(scale), scale)
         else:
             sc[3] = 1.0
             if self.clip_mode == "value":
                 g = g.clamp(-self.clip, self.clip)
-            g = torch.where(skip, torch.zeros_like(g), g)
         t = torch.clamp(sc[1], min=1.0)
         lr_t = sc[0] * torch.sqrt(1.0 - self.b2 ** t) / (1.0 - self.b1 ** t) * keep
         b1 = 1.0 - (1.0 - self.b1) * keep

@@ -61,3 +61,138 @@ def test_fused_latent_matches_torch_ops(dec_model, kl_tol, given_eps):
     for n in gu:
         d = float((gf[n] - gu[n]).norm() / gu[n].norm().clamp_min(1e-12))
         assert d < 1e-2, (n, d)
+
+
+# ---------------------------------------------------------------------------------
+# ops.latent.latent called directly, against the docstring formula in fp64
+# ---------------------------------------------------------------------------------
+K_ENC = 64                      # encoder width: small keeps the three GEMMs quick
+STREAM = 11
+PARAMS = ("h", "W_mu", "b_mu", "W_sig", "b_sig", "W_init", "b_init")
+# (B, Z, widths): n = B*Z = 24 < the 1024 threads of latent_mid, one segment;
+# n = 4736, not a multiple of 1024, four unequal segments in the hyper layout;
+# the production n = 12800. (small_mm takes every one of these shapes.)
+LATENT_SHAPES = [(3, 8, (40,)), (37, 128, (96, 32, 96, 32)), (100, 128, (512, 512))]
+KL_TOL = {"above": 0.02, "below": 5.0}   # raw KL ~0.2 with the weights below: clearly above / below
+# upstream-gradient patterns: which outputs reach the loss
+#            segments         kl     z      mu, presig
+PATTERNS = {
+    "all": ("all", True, True, True),
+    "segments_and_kl": ("all", True, False, False),      # dz, dmu, dps None
+    "kl_unused": ("all", False, True, False),            # dkl None
+    "one_segment_unused": ("drop", True, True, False),   # that segment's gradient None
+    "mu_presig_direct": ("all", True, False, True),      # dmu_ext / dps_ext, as score-style consumers
+}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report():
+    import fp64_rule as R
+    yield
+    R.report("latent node (csrc/latent.hip)")
+
+
+def _latent_inputs(B, Z, widths):
+    g = torch.Generator(device=DEV).manual_seed(B * 1000 + Z)
+    S = sum(widths)
+    r = lambda *s: torch.randn(*s, generator=g, device=DEV)   # noqa: E731
+    inp = {"h": r(B, K_ENC), "W_mu": r(K_ENC, Z) * (0.5 / K_ENC ** 0.5), "b_mu": 0.1 * r(Z),
+           "W_sig": r(K_ENC, Z) * (0.5 / K_ENC ** 0.5), "b_sig": 0.1 * r(Z),
+           "W_init": r(Z, S) / Z ** 0.5, "b_init": 0.1 * r(S)}
+    # fixed random upstream gradients: one per output
+    up = {"mu": r(B, Z), "presig": r(B, Z), "z": r(B, Z), "kl": r(()) + 2.0, "segs": [r(B, w) for w in widths]}
+    return inp, up, r(B, Z)
+
+
+def _latent_formula(p, eps, widths, kl_tol):
+    """The docstring of ops/latent.py, in the dtype of ``p``."""
+    mu = p["h"] @ p["W_mu"] + p["b_mu"]
+    presig = p["h"] @ p["W_sig"] + p["b_sig"]
+    z = mu + torch.exp(presig / 2.0) * eps
+    raw = -0.5 * torch.mean(1.0 + presig - mu * mu - torch.exp(presig))
+    kl = torch.maximum(raw, torch.full_like(raw, kl_tol))
+    segs = torch.split(torch.tanh(z @ p["W_init"] + p["b_init"]), list(widths), dim=1)
+    return (mu, presig, z, kl, *segs), raw
+
+
+def _latent_loss(out, up, spec, dtype):
+    segs_used, use_kl, use_z, use_mu = spec
+    mu, presig, z, kl, *segs = out
+    drop = len(segs) - 1 if len(segs) == 1 else 1   # the unused segment
+    loss = 0.0
+    for k, (s, u) in enumerate(zip(segs, up["segs"])):
+        if segs_used == "all" or k != drop:
+            loss = loss + (s * u.to(dtype)).sum()
+    if use_kl:
+        loss = loss + kl * up["kl"].to(dtype)
+    if use_z:
+        loss = loss + (z * up["z"].to(dtype)).sum()
+    if use_mu:
+        loss = loss + (mu * up["mu"].to(dtype)).sum() + (presig * up["presig"].to(dtype)).sum()
+    return loss
+
+
+def _latent_run(kind, inp, up, eps, widths, kl_tol, spec, seed):
+    """``kind``: "kernel" | torch.float32 | torch.float64. Returns (outputs, grads, raw KL)."""
+    dtype = torch.float32 if kind == "kernel" else kind
+    p = {k: v.to(dtype).clone().requires_grad_() for k, v in inp.items()}
+    if kind == "kernel":
+        from sketch_rnn_amd.ops.latent import latent
+        ops.set_backend("hip")
+        out = latent(p["h"], p["W_mu"], p["b_mu"], p["W_sig"], p["b_sig"], p["W_init"], p["b_init"], seed, widths,
+                     kl_tol, STREAM, eps=eps)
+        raw = None
+    else:
+        if eps is None:
+            from sketch_rnn_amd.models.cells import hash_normal
+            eps = hash_normal(seed, STREAM, 0, (inp["h"].shape[0], inp["W_mu"].shape[1]))
+        out, raw = _latent_formula(p, eps.to(dtype), widths, kl_tol)
+    grads = torch.autograd.grad(_latent_loss(out, up, spec, dtype), [p[k] for k in PARAMS], allow_unused=True)
+    # (a reference whose only segment is unused never reaches W_init / b_init: zero gradients)
+    grads = [torch.zeros_like(p[k]) if g is None else g for k, g in zip(PARAMS, grads)]
+    torch.cuda.synchronize()
+    return [o.detach() for o in out], dict(zip(PARAMS, grads)), raw
+
+
+@pytest.mark.parametrize("regime", ["above", "below"])
+@pytest.mark.parametrize("given_eps", [True, False], ids=["eps_given", "eps_hashed"])
+@pytest.mark.parametrize("B,Z,widths", LATENT_SHAPES)
+def test_latent_node_matches_fp64_formula(B, Z, widths, given_eps, regime):
+    """Forward outputs and all seven gradients per upstream-gradient pattern
+    (the None paths ``set_materialize_grads(False)`` creates in the backward),
+    under the rule of tests/fp64_rule.py. Below the tolerance ``kl`` is the
+    tolerance itself and the KL term adds exactly nothing to any gradient.
+    Largest err_k / err_32 measured on an MI355X (margin 4 everywhere): db_sig
+    5.13 and dW_sig 4.11 -- there err_32 is itself below the 4 * 2^-24 max|q64|
+    term, and they use 0.61 / 0.57 of the bound -- z 2.99, dW_init 2.83, presig
+    2.44, mu 2.38, dh 2.21, segments 2.02, db_init 1.90, db_mu 1.84, dW_mu 1.70,
+    kl 1.00."""
+    import fp64_rule as R
+    inp, up, eps = _latent_inputs(B, Z, widths)
+    eps = eps if given_eps else None
+    seed = torch.tensor([9], device=DEV)
+    kl_tol = KL_TOL[regime]
+    names = ["mu", "presig", "z", "kl"] + ["segment"] * len(widths)
+    kernel = {}
+    for pattern, spec in PATTERNS.items():
+        ok, gk, _ = _latent_run("kernel", inp, up, eps, widths, kl_tol, spec, seed)
+        o32, g32, _ = _latent_run(torch.float32, inp, up, eps, widths, kl_tol, spec, seed)
+        o64, g64, raw64 = _latent_run(torch.float64, inp, up, eps, widths, kl_tol, spec, seed)
+        raw64 = float(raw64.detach())
+        assert raw64 >= 1.1 * kl_tol if regime == "above" else raw64 <= 0.9 * kl_tol, (raw64, kl_tol)
+        for n, a, b, c in zip(names, ok, o32, o64):
+            R.check("latent %s" % n, a.reshape(-1), b.reshape(-1), c.reshape(-1))
+        if regime == "below":
+            assert ok[3].item() == torch.tensor(kl_tol, dtype=torch.float32).item()
+        for n in PARAMS:
+            R.check("latent d%s" % n, gk[n], g32[n], g64[n])
+        if pattern == "one_segment_unused":   # its columns of dpre are exactly 0
+            k = 0 if len(widths) == 1 else 1
+            c0 = sum(widths[:k])
+            assert not bool(gk["W_init"][:, c0:c0 + widths[k]].any())
+            assert not bool(gk["b_init"][c0:c0 + widths[k]].any())
+        kernel[pattern] = gk
+    if regime == "below":   # "all" with the KL term removed (dkl None): bitwise the same gradients
+        _, g0, _ = _latent_run("kernel", inp, up, eps, widths, kl_tol, ("all", False, True, True), seed)
+        for n in PARAMS:
+            assert torch.equal(kernel["all"][n], g0[n]), n

@@ -74,6 +74,18 @@ def test_fused_head_upstream_grads():
         assert _rel(a, r) < 3e-2, (n, _rel(a, r))
 
 
+@pytest.mark.parametrize("coef", [(0.7, 1.3, -0.4), (0.5, 0.0, 0.0)], ids=["split_scales", "one_scale"])
+def test_fused_head_upstream_grads_with_dropout(coef):
+    """The upstream scales multiply fp32 sums inside the backward kernels (the
+    pen columns of dX apart, when their scale differs): the same result with
+    the input dropout mask applied after them."""
+    x, W, b, t = _data(300, 256, 20, "reference", 6)
+    fu = _run(True, x, W, b, t, 20, "reference", 0.8, coef)
+    ref = _run(False, x, W, b, t, 20, "reference", 0.8, coef)
+    for n, a, r in zip(["dx", "dW", "db"], fu[3:], ref[3:]):
+        assert _rel(a, r) < 3e-2, (n, _rel(a, r))
+
+
 def test_fused_head_is_deterministic():
     x, W, b, t = _data(2000, 512, 20, "magenta", 4)
     r1 = _run(True, x, W, b, t, 20, "magenta", 0.9, (1.0, 0.0, 0.0))

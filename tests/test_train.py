@@ -284,21 +284,33 @@ def test_cli_smoke(tmp_path):
     assert os.path.exists(root + "/v.svg")
 
 
-def test_flat_adam_nonfinite_skip_and_apply():
+def _bits(x):
+    return x.detach().clone().view(torch.int32)
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")], ids=["nan", "inf"])
+@pytest.mark.parametrize("clip_mode,clip", [("value", 1.0), ("global_norm", 1.0), (None, 0.0)])
+def test_flat_adam_nonfinite_skip_and_apply(clip_mode, clip, bad):
     ps = _params()
-    opt = FlatAdam(ps, lr=0.1, clip_mode="value", clip=1.0, nonfinite="skip")
+    opt = FlatAdam(ps, lr=0.1, clip_mode=clip_mode, clip=clip, nonfinite="skip")
     for p in ps:
         p.grad.fill_(0.5)
     opt.step()
     before = opt.flat.clone()
     m0 = opt.m.clone()
-    ps[0].grad[0, 0] = float("nan")
+    flat_b, m_b, v_b = _bits(opt.flat), _bits(opt.m), _bits(opt.v)
+    ps[0].grad[0, 0] = bad
     opt.step()
     assert torch.equal(opt.flat, before) and torch.equal(opt.m, m0)
+    # bitwise: a skipped step is a no-op on the parameters and both moments
+    assert torch.equal(_bits(opt.flat), flat_b) and torch.equal(_bits(opt.m), m_b)
+    assert torch.equal(_bits(opt.v), v_b)
+    assert not math.isfinite(float(opt.scalars[2]))
     assert int(opt.scalars[1]) == 1 and opt.skipped_steps() == 1 and int(opt.scalars[4]) == 1
     ps[0].grad[0, 0] = 0.5
     opt.step()
     assert int(opt.scalars[1]) == 2 and int(opt.scalars[4]) == 0 and not torch.equal(opt.flat, before)
+    assert torch.isfinite(opt.flat).all() and torch.isfinite(opt.m).all() and torch.isfinite(opt.v).all()
     ps2 = _params()
     opt2 = FlatAdam(ps2, lr=0.1, nonfinite="apply")
     for p in ps2:
