@@ -496,9 +496,6 @@ class HipLib:
         lib.skr_hyper_mod_fwd.argtypes = [_p, _i64, _p, _p, _p, _p, _i64, _i, _p, _p, _p, _p, _i, _i, _i,
                                           C.POINTER(ModDecode), _p]
         lib.skr_hyper_mod_fwd.restype = _i
-        lib.skr_hyper_mod_chain.argtypes = [_p, _i64, _p, _p, _p, _i, _p, _i64, _i, _p, _p, C.POINTER(LstmFwdArgs),
-                                            C.POINTER(ChainSync), _p]
-        lib.skr_hyper_mod_chain.restype = _i
         lib.skr_hyper_cell_mod.argtypes = [C.POINTER(LstmFwdArgs), _p, _p, _p, _i, _p, _i64, _i, _p, _p, _p, _p, _i,
                                            C.POINTER(ChainSync), _p]
         lib.skr_hyper_cell_mod.restype = _i

@@ -68,24 +68,15 @@ CHAIN3 = False
 # (profiles/r6/chain_fwd_ab.log) -- the two exchanges (each both
 # workgroups' arrival) cost more than the halved per-CU stream saves.
 CHAIN_CL = 1
-# Chained forward step (csrc/hyper_mod.hip skr_hyper_mod_chain): the main
-# LayerNorm cell rows of step t run INSIDE step t's modulation launch -- every
-# workgroup runs its modulation tile, arrives, and the first B * CHAIN_FWD_C
-# then run the main cell over H / CHAIN_FWD_C units of one row (their c_prev
-# and LayerNorm-parameter loads issued before the in-launch wait): three
-# launches per forward step instead of four. Tested (oracle, poison, repeat),
-# OFF: measured on MI355X (same box, A B C A B C, profiles/r6/chain_fwd_ab.log)
-# 24.01 / 24.04 ms/step (C = 2) and 24.23 / 24.26 (C = 1) against 23.91 /
-# 23.89 for the two launches: the chained launch takes 19.75 us per step
-# against 10.5 + 8.8 for the pair -- the grid-wide arrival costs what the
-# kernel boundary did, and the rows cannot keep the faster four-workgroup
-# geometry (B * 4 > the 256 resident modulation workgroups).
-CHAIN_FWD = False
-CHAIN_FWD_C = 2
-CHAIN_FWD_STATS = {"launches": 0}
-# Debug (tests): NaN-fill the d[h | hh] slabs before every chained launch (and
-# g / its partial sums before every chained forward launch), so a main-cell
-# row that read them ahead of its producer tiles shows up as NaN.
+# (Round 6 measured the main-cell rows of step t inside step t's modulation
+# launch -- every workgroup ran its modulation tile, arrived, and the first
+# rows' worth then ran the main cell after an in-launch wait -- at 24.01 /
+# 24.04 ms/step with two workgroups per row and 24.23 / 24.26 with one,
+# against 23.91 / 23.89 for the two launches: 19.75 us per step against
+# 10.5 + 8.8 for the pair. profiles/r6/chain_fwd_ab.log; removed, its code is
+# last in commit 763b0d2.)
+# Debug (tests): NaN-fill the d[h | hh] slabs before every chained launch, so
+# a main-cell row that read them ahead of its producer tiles shows up as NaN.
 CHAIN_POISON = False
 # Hyper cell + modulation step in ONE forward launch (csrc/hyper_mod.hip
 # hyper_cell_mod): wave 0 of modulation workgroup b runs the hyper cell of row
@@ -383,14 +374,9 @@ class _HyperSeq(torch.autograd.Function):
         am.forget_bias, am.keep = float(forget_bias), float(keep)
         am.seed, am.stream = sd.data_ptr(), int(stream)
         am.ld_lp, am.lp_kind = K, _lp_kind(A)
-        # chained modulation + main cell (one row block, LayerNorm main cell, no fp8 copy)
-        chain_f = CHAIN_FWD and hmod and mln_on and B <= 128 and T >= 2 and H % max(CHAIN_FWD_C, 1) == 0
-        cf = gemm.ChainCounters(dev, "hyp_fwd_m", T) if chain_f else None
-        cell_mod = CELL_MOD and hmod and not chain_f and 65 <= B <= 128 and T >= 2 and Hh == 256 and \
-            _lp_kind(A) == 1
+        cell_mod = CELL_MOD and hmod and 65 <= B <= 128 and T >= 2 and Hh == 256 and _lp_kind(A) == 1
         cmc = gemm.ChainCounters(dev, "hyp_cell_mod", T) if cell_mod else None
-        clm = _ClusterSync(T, B, H, dev, ln=mln_on,
-                           C=(max(CHAIN_FWD_C, 1) if chain_f else HYPER_MAIN_C) if hmod else 0)
+        clm = _ClusterSync(T, B, H, dev, ln=mln_on, C=HYPER_MAIN_C if hmod else 0)
         clh = _ClusterSync(T, B, Hh, dev)
         st = _stream()
         group = gemm.GROUPED and S_m >= 1 and S_y >= 1 and dt == torch.bfloat16
@@ -425,24 +411,6 @@ class _HyperSeq(torch.autograd.Function):
             am.h_lp, am.c_carry = A[t + 1, :, :H].data_ptr(), CC[t + 1].data_ptr()
             if hmod:
                 am.gpre, am.gstats, am.gstat_tiles = GP.data_ptr(), GS.data_ptr(), H // 32
-            if chain_f:   # modulation tiles -> this step's main cell rows, one launch
-                if CHAIN_POISON:
-                    GP.fill_(float("nan"))
-                    GS.fill_(float("nan"))
-                rc = lib.lib.skr_hyper_mod_chain(A[t + 1, :, H:].data_ptr(), K, PlT.data_ptr(), qb.data_ptr(),
-                                                 XHc[t].data_ptr(), xh_dec.xh_bf16, RM[rmi(t)].data_ptr(), B * G, S_m,
-                                                 VEC[t].data_ptr(), _ptr(RLP[t] if RLP is not None else None),
-                                                 ctypes.byref(am), ctypes.byref(cf.at(t)), st)
-                if rc == 0:
-                    CHAIN_FWD_STATS["launches"] += 1
-                    continue
-                if rc not in (-2, -3, -4, -8):
-                    _check(rc, "hyper_mod_chain")
-                # shape or residency not taken: two launches from here on (the
-                # counters of launches 0 .. t-1 are cleared for the next sequence;
-                # the cluster buffer keeps its C: the MOD-3 cell takes C = 2 too)
-                chain_f = False
-                cf.buf.zero_()
             if cell_mod:   # hyper cell rows + modulation tiles, one launch
                 if CELL_MOD_POISON:
                     A[t + 1, :, H:].fill_(float("nan"))
