@@ -14,7 +14,9 @@
 //        fold_head_slabs), wave 0 draws the stroke (mdn_sample_wave: the same
 //        keyed hash draws as skr_mdn_sample_slabs, so a stroke is the same
 //        whichever kernel samples it), lane 0 writes out[b][t-1], done[b]
-//        and x[b]; the 5 values meet the rest of the workgroup in LDS;
+//        and x[b]; the 5 values meet the rest of the workgroup in LDS; a
+//        forced row (sketch completion, mdn_sample.h) takes its given
+//        stroke instead of the draw;
 //        (sampling off) x[b] is read (t == 0, or teacher-forced steps);
 //     2. the hyper LayerNorm cell (cell_fwd_body.h's arithmetic) with its
 //        x-projection formed in-register from x (zp + x . w5, the per-sketch
@@ -34,6 +36,8 @@ struct DecodeSample {
     const int64_t* seed; uint32_t step; int row0;            // hash key (global row = row0 + b)
     float* out_row; int64_t ld_out;    // out[b] = stroke of step `step` (row stride ld_out)
     int* done;                         // [B] eos reached
+    const float* forced; int64_t ld_forced;   // rows with step < nforced[b] emit forced[b] instead of
+    const int* nforced;                // their draw (mdn_sample.h; nullptr: none)
 };
 
 namespace {
@@ -69,6 +73,7 @@ __global__ __launch_bounds__(256) void decode_hyper_cell(const FwdArgs a, const 
     }
     const float lcg = a.lnc_g[u], lcb = a.lnc_b[u];
     const float cp = a.c_prev[(int64_t)b * H + u];
+    const float fv = skr::mdn_forced_load(s.forced, s.ld_forced, s.active ? s.nforced : nullptr, b);
     // ---- stroke t-1: fold + draw (or the given x)
     if (s.active) {
         skr::fold_head_slabs(s.zs, s.ldz, s.nslab, s.slab, s.bias, s.nout, b, part, zrow);
@@ -76,17 +81,8 @@ __global__ __launch_bounds__(256) void decode_hyper_cell(const FwdArgs a, const 
             const uint32_t key = skr::hash_key(*s.seed, 0x5A3Du, s.step);
             const skr::MdnDraw d =
                 skr::mdn_sample_wave(zrow, s.M, s.mode, s.temp, s.greedy, s.fix_pen, key, (uint32_t)(s.row0 + b), s.step);
-            if (lane == 0) {
-                const int stop_col = s.mode == 1 ? 4 : 3;   // p3 | eoc
-                float* o = s.out_row + b * s.ld_out;
-                const bool was_done = s.done[b] != 0;
-                for (int k = 0; k < 5; ++k) {
-                    o[k] = was_done ? (k == stop_col ? 1.f : 0.f) : d.row[k];
-                    x[b * 5 + k] = d.row[k];
-                    xr[k] = d.row[k];
-                }
-                if (d.pidx + 2 == stop_col) s.done[b] = 1;
-            }
+            const skr::MdnForced fz = skr::mdn_forced_gather(fv);
+            if (lane == 0) skr::mdn_emit_row(d, fz, s.step, s.mode, s.out_row + b * s.ld_out, x + b * 5, s.done + b, xr);
         }
     } else if (tid < 5) {
         xr[tid] = x[b * 5 + tid];
@@ -142,7 +138,7 @@ SKR_API int skr_decode_hyper_cell(const FwdArgs* a, const DecodeSample* s, float
         a->reset != nullptr || a->xhat != nullptr || a->act != nullptr || a->c_carry == nullptr)
         return -2;
     if (s->active && (s->nout > 256 || s->M > 64 || s->nslab < 1 || s->zs == nullptr || s->done == nullptr ||
-                      s->out_row == nullptr || s->seed == nullptr))
+                      s->out_row == nullptr || s->seed == nullptr || (s->nforced != nullptr && s->forced == nullptr)))
         return -3;
     const dim3 grid(a->B), blk(256);
     switch (a->R_nslab) {

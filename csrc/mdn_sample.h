@@ -109,6 +109,76 @@ __device__ inline MdnDraw mdn_sample_wave(const float* zr, int M, int mode, floa
     return d;
 }
 
+// Forced strokes (sketch completion): row b at stroke index `step` is forced
+// iff nforced != nullptr && step < nforced[b]. A forced row emits the five
+// floats of forced[b * ld_forced ..] bit for bit instead of its draw, as the
+// output row and as the next decoder input; it takes the finished state from
+// that row's stop column (the rule of csrc/decode_vae.hip) and never emits
+// padding. A select, never a blend: nothing of the head output reaches a
+// forced row's result.
+struct MdnForced {
+    int n;          // nforced[b] (0: no forced strokes)
+    float row[5];   // forced[b]
+    __device__ bool on(uint32_t step) const { return (int64_t)step < (int64_t)n; }
+};
+
+// The loads of row b's forced stroke, held across wave 0: lane k < 5 gets
+// forced[b][k], lane 5 the bits of nforced[b] (0 when nforced is null). Callers
+// issue it with their other early loads, before the slab fold and the draw.
+// Per-lane vector loads whose only condition is the kernel argument `nforced`:
+// nothing waits for them until mdn_forced_gather -- a wave-uniform scalar
+// load of nforced[b] would be awaited on the spot, one memory latency in front
+// of the fold. forced[b] must be readable for every row whenever nforced is
+// given, forced row or not.
+__device__ inline float mdn_forced_load(const float* __restrict__ forced, int64_t ld_forced,
+                                        const int* __restrict__ nforced, int b) {
+    const int lane = threadIdx.x;           // wave 0 samples in every kernel: the other waves load nothing
+    float v = 0.f;
+    if (nforced != nullptr && lane < 6) {   // one load, its address chosen per lane (so it stays a vector load)
+        const float* fr = forced + (int64_t)b * ld_forced + lane;
+        v = *(lane < 5 ? fr : reinterpret_cast<const float*>(nforced + b));
+    }
+    return v;
+}
+
+// Every lane of the wave must be active; the result is wave-uniform.
+__device__ inline MdnForced mdn_forced_gather(float v) {
+    MdnForced f;
+    const int bits = __float_as_int(v);
+    f.n = __builtin_amdgcn_readlane(bits, 5);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) f.row[k] = __int_as_float(__builtin_amdgcn_readlane(bits, k));
+    return f;
+}
+
+// One lane's epilogue of a sampled row: o = the emitted stroke (padding for a
+// finished row), nx = the next decoder input (and xr, its LDS copy, when
+// given), *done set when the row stops (never cleared).
+__device__ inline void mdn_emit_row(const MdnDraw& d, const MdnForced& f, uint32_t step, int mode, float* o,
+                                    float* nx, int* done, float* xr = nullptr) {
+    const int stop_col = mode == 1 ? 4 : 3;  // p3 | eoc
+    const bool on = f.on(step);
+    const bool pad = !on && *done != 0;      // finished rows emit end-of-sketch padding
+    // The draw ends here as it ends at a store: the selects below must not reach
+    // back into its arithmetic (paired with dx, dy's last product would be
+    // contracted differently, and a draw must keep its bits in every kernel).
+    float dr[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        dr[k] = d.row[k];
+        asm volatile("" : "+v"(dr[k]));
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const float v = on ? f.row[k] : dr[k];
+        o[k] = pad ? (k == stop_col ? 1.f : 0.f) : v;
+        nx[k] = v;
+        if (xr) xr[k] = v;
+    }
+    const bool stop = on ? (mode == 1 ? f.row[4] : f.row[3]) > 0.f : d.pidx + 2 == stop_col;
+    if (stop) *done = 1;
+}
+
 // Head output row b as the sum of `nslab` split-K partial slabs of the head
 // GEMM (csrc/skinny_gemm.hip, z = h @ W_out, no bias) plus the bias, by a
 // 256-thread workgroup: wave w folds the slabs s = w mod 4 of every column

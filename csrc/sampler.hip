@@ -14,6 +14,10 @@
 //          pen from step 0; sigma scaled by the temperature; a row stops after
 //          emitting p3.
 // greedy: argmax component / pen, offset = mean.
+//
+// Sketch completion: the *_forced entry points take per-row given strokes;
+// a row with step < nforced[b] emits forced[b] instead of its draw
+// (mdn_sample.h: MdnForced, mdn_emit_row).
 #include "mdn_sample.h"
 
 namespace {
@@ -22,25 +26,17 @@ __global__ __launch_bounds__(64) void mdn_sample_kernel(const float* __restrict_
                                                         float temp, int greedy, int fix_pen, const int64_t* seed,
                                                         uint32_t step, float* __restrict__ out_row, int64_t ld_out,
                                                         float* __restrict__ next_x, int64_t ld_next,
-                                                        int* __restrict__ done, float* __restrict__ params) {
+                                                        int* __restrict__ done, float* __restrict__ params,
+                                                        const float* __restrict__ forced, int64_t ld_forced,
+                                                        const int* __restrict__ nforced) {
     const int b = blockIdx.x, lane = threadIdx.x;
+    const float fv = skr::mdn_forced_load(forced, ld_forced, nforced, b);
     const uint32_t key = skr::hash_key(*seed, 0x5A3Du, step);
     const skr::MdnDraw d = skr::mdn_sample_wave(z + b * ldz, M, mode, temp, greedy, fix_pen, key, (uint32_t)b, step);
+    const skr::MdnForced f = skr::mdn_forced_gather(fv);
     if (lane != 0) return;
-    const bool was_done = done[b] != 0;
-    float* o = out_row + b * ld_out;
-    if (was_done) {
-        // finished rows emit end-of-sketch padding
-        for (int k = 0; k < 5; ++k) o[k] = 0.f;
-        o[mode == 1 ? 4 : 3] = 1.f;
-    } else {
-        for (int k = 0; k < 5; ++k) o[k] = d.row[k];
-    }
-    float* nx = next_x + b * ld_next;
-    for (int k = 0; k < 5; ++k) nx[k] = d.row[k];
-    const int stop_col = mode == 1 ? 4 : 3;  // p3 | eoc
-    if (d.pidx + 2 == stop_col) done[b] = 1;
-    if (params) {
+    skr::mdn_emit_row(d, f, step, mode, out_row + b * ld_out, next_x + b * ld_next, done + b);
+    if (params) {   // (of the draw, forced row or not)
         float* p = params + b * 4;
         p[0] = (float)d.idx;
         p[1] = (float)d.pidx;
@@ -60,43 +56,64 @@ __global__ __launch_bounds__(256) void mdn_sample_slabs_kernel(const float* __re
                                                                const int64_t* seed, uint32_t step, int row0,
                                                                float* __restrict__ out_row, int64_t ld_out,
                                                                float* __restrict__ next_x, int64_t ld_next,
-                                                               int* __restrict__ done) {
+                                                               int* __restrict__ done,
+                                                               const float* __restrict__ forced, int64_t ld_forced,
+                                                               const int* __restrict__ nforced) {
     __shared__ float part[4][256];
     __shared__ float zrow[256];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const float fv = skr::mdn_forced_load(forced, ld_forced, nforced, b);
     skr::fold_head_slabs(zs, ldz, nslab, slab, bias, nout, b, part, zrow);
     if (w != 0) return;
     const uint32_t key = skr::hash_key(*seed, 0x5A3Du, step);
     const skr::MdnDraw d = skr::mdn_sample_wave(zrow, M, mode, temp, greedy, fix_pen, key, (uint32_t)(row0 + b), step);
+    const skr::MdnForced f = skr::mdn_forced_gather(fv);
     if (lane != 0) return;
-    const int stop_col = mode == 1 ? 4 : 3;  // p3 | eoc
-    float* o = out_row + b * ld_out;
-    const bool was_done = done[b] != 0;
-    for (int k = 0; k < 5; ++k) o[k] = was_done ? (k == stop_col ? 1.f : 0.f) : d.row[k];
-    float* nx = next_x + b * ld_next;
-    for (int k = 0; k < 5; ++k) nx[k] = d.row[k];
-    if (d.pidx + 2 == stop_col) done[b] = 1;
+    skr::mdn_emit_row(d, f, step, mode, out_row + b * ld_out, next_x + b * ld_next, done + b);
 }
 
 }  // namespace
+
+// forced [B][ld_forced] / nforced [B] (indexed like `done`, by local row): rows
+// with step < nforced[b] emit forced[b] instead of their draw (mdn_sample.h;
+// every row of forced is read when nforced is given).
+SKR_API int skr_mdn_sample_slabs_forced(const float* zs, int64_t ldz, int nslab, int64_t slab, const float* bias, int B,
+                                        int M, int mode, float temp, int greedy, int fix_pen, const int64_t* seed,
+                                        uint32_t step, int row0, float* out_row, int64_t ld_out, float* next_x,
+                                        int64_t ld_next, int* done, const float* forced, int64_t ld_forced,
+                                        const int* nforced, hipStream_t s) {
+    if (M < 1 || M > 32 || nslab < 1) return -2;
+    if (nforced != nullptr && forced == nullptr) return -2;
+    if (B <= 0) return 0;
+    hipLaunchKernelGGL(mdn_sample_slabs_kernel, dim3(B), dim3(256), 0, s, zs, ldz, nslab, slab, bias, 3 + 6 * M, M,
+                       mode, temp, greedy, fix_pen, seed, step, row0, out_row, ld_out, next_x, ld_next, done, forced,
+                       ld_forced, nforced);
+    return SKR_CHECK_LAUNCH();
+}
 
 SKR_API int skr_mdn_sample_slabs(const float* zs, int64_t ldz, int nslab, int64_t slab, const float* bias, int B,
                                  int M, int mode, float temp, int greedy, int fix_pen, const int64_t* seed,
                                  uint32_t step, int row0, float* out_row, int64_t ld_out, float* next_x,
                                  int64_t ld_next, int* done, hipStream_t s) {
-    if (M < 1 || M > 32 || nslab < 1) return -2;
+    return skr_mdn_sample_slabs_forced(zs, ldz, nslab, slab, bias, B, M, mode, temp, greedy, fix_pen, seed, step, row0,
+                                       out_row, ld_out, next_x, ld_next, done, nullptr, 0, nullptr, s);
+}
+
+SKR_API int skr_mdn_sample_forced(const float* z, int64_t ldz, int B, int M, int mode, float temp, int greedy,
+                                  int fix_pen, const int64_t* seed, uint32_t step, float* out_row, int64_t ld_out,
+                                  float* next_x, int64_t ld_next, int* done, float* params, const float* forced,
+                                  int64_t ld_forced, const int* nforced, hipStream_t s) {
+    if (M < 1 || M > 32) return -2;
+    if (nforced != nullptr && forced == nullptr) return -2;
     if (B <= 0) return 0;
-    hipLaunchKernelGGL(mdn_sample_slabs_kernel, dim3(B), dim3(256), 0, s, zs, ldz, nslab, slab, bias, 3 + 6 * M, M,
-                       mode, temp, greedy, fix_pen, seed, step, row0, out_row, ld_out, next_x, ld_next, done);
+    hipLaunchKernelGGL(mdn_sample_kernel, dim3(B), dim3(64), 0, s, z, ldz, M, mode, temp, greedy, fix_pen, seed, step,
+                       out_row, ld_out, next_x, ld_next, done, params, forced, ld_forced, nforced);
     return SKR_CHECK_LAUNCH();
 }
 
 SKR_API int skr_mdn_sample(const float* z, int64_t ldz, int B, int M, int mode, float temp, int greedy, int fix_pen,
                            const int64_t* seed, uint32_t step, float* out_row, int64_t ld_out, float* next_x,
                            int64_t ld_next, int* done, float* params, hipStream_t s) {
-    if (M < 1 || M > 32) return -2;
-    if (B <= 0) return 0;
-    hipLaunchKernelGGL(mdn_sample_kernel, dim3(B), dim3(64), 0, s, z, ldz, M, mode, temp, greedy, fix_pen, seed, step,
-                       out_row, ld_out, next_x, ld_next, done, params);
-    return SKR_CHECK_LAUNCH();
+    return skr_mdn_sample_forced(z, ldz, B, M, mode, temp, greedy, fix_pen, seed, step, out_row, ld_out, next_x,
+                                 ld_next, done, params, nullptr, 0, nullptr, s);
 }

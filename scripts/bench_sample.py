@@ -22,6 +22,9 @@ line with
 (random-init models end their sketches after a handful of strokes, which
 makes every throughput look like padding).
 
+``--prefix_len P`` (sketch completion, both ``--impl`` arms) feeds a synthetic
+P-stroke pen-down prefix to every row; the decoder continues from it.
+
 usage: python scripts/bench_sample.py [--config vae_large] [--batch 256] [--steps 250] [--train-steps 0]
 """
 from __future__ import annotations
@@ -50,7 +53,11 @@ def main():
     ap.add_argument("--impl", default="graph", choices=["graph", "fused"],
                     help="graph: GraphDecoder; fused: the whole-sketch kernel (fused_vae_decoder: plain lstm and "
                          "layer_norm decoders)")
+    ap.add_argument("--prefix_len", type=int, default=0,
+                    help="feed a synthetic prefix of this many strokes to every row (sketch completion)")
     a = ap.parse_args()
+    if not 0 <= a.prefix_len <= a.steps:
+        ap.error("--prefix_len must lie in [0, --steps]")
     import numpy as np
     import torch
     from sketch_rnn_amd import ops
@@ -78,23 +85,30 @@ def main():
         model = tr.model.eval()
     else:
         model = SketchVAE(cfg, seed=0).cuda().eval()
+    pre = {}
+    if a.prefix_len > 0:       # pen-down strokes of the data's scale (unit offsets)
+        p5 = torch.zeros(a.batch, a.prefix_len, 5, device="cuda")
+        p5[..., :2] = torch.randn(a.batch, a.prefix_len, 2, device="cuda",
+                                  generator=torch.Generator(device="cuda").manual_seed(0)) * 0.5
+        p5[..., 2] = 1.0
+        pre = dict(prefix=p5)
     dec, impl = None, a.impl
     if a.impl == "fused":
         from sketch_rnn_amd.sample.fused import NotCoResident, fused_vae_decoder
         try:
             dec = fused_vae_decoder(model, a.batch, a.steps, a.temperature, early_exit=not a.no_early_exit)
-            dec.run(seed=0)
+            dec.run(seed=0, **pre)
         except (ValueError, NotCoResident) as e:
             print("--impl fused: %s; using the graph decoder" % e, file=sys.stderr)
             dec, impl = None, "graph"
     if dec is None:
         dec = GraphDecoder(model, a.batch, a.steps, a.temperature, early_exit=not a.no_early_exit, fp8=a.fp8)
-    dec.run(seed=0)  # capture
+    dec.run(seed=0, **pre)  # capture
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     total_len = total_pos = 0
     for r in range(a.reps):
-        s, lens = dec.run(seed=r + 1)
+        s, lens = dec.run(seed=r + 1, **pre)
         total_len += int(lens.sum())
         total_pos += a.batch * dec.steps_run
     torch.cuda.synchronize()
@@ -109,7 +123,7 @@ def main():
     valid_sps = total_len / wall
     print(json.dumps({"metric": "sampled valid strokes/sec (temperature %.2f)" % a.temperature, "config": a.config,
                       "impl": impl, "dtype": a.dtype, "fp8_gemm": bool(a.fp8), "batch": a.batch, "steps": a.steps, "train_steps": a.train_steps,
-                      "train_cost": train_cost, "early_exit": not a.no_early_exit,
+                      "train_cost": train_cost, "early_exit": not a.no_early_exit, "prefix_len": a.prefix_len,
                       "valid_strokes_per_s": round(valid_sps, 1),
                       "decode_positions_per_s": round(total_pos / wall, 1),
                       "steps_run": total_pos / a.batch / a.reps,

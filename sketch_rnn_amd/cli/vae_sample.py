@@ -2,16 +2,34 @@
 
 Modes: ``random`` (z ~ N(0, I), or the unconditional decoder), ``class``
 (class-conditional z for ``--label``), ``interpolate`` (spherical
-interpolation between two random latents). Writes a stroke-3 SVG grid.
+interpolation between two random latents), and two modes that read
+sketches from a dataset (``--data`` / ``--synthetic`` / ``--split`` as in
+``cli.vae_eval``, ``--offset`` for the first sketch):
+
+* ``reconstruct`` -- encode each of ``--n`` sketches and decode it again:
+  ``z`` is the encoder's ``mu`` (``--sample_z``: ``mu + sigma * eps``), the
+  class label is the sketch's. The grid holds each original followed by its
+  reconstruction. Needs a conditional model.
+* ``complete`` -- feed the first ``ceil(prefix_frac * len)`` strokes of each
+  sketch (at most ``len - 1``) to the decoder and let it finish the drawing,
+  ``--completions K`` times per sketch. ``--z_from`` picks the latent of a
+  conditional model: the encoded ``prefix`` (default), the encoded ``full``
+  sketch, or the ``prior``. The grid holds each prefix followed by its K
+  completions.
+
+Writes a stroke-3 SVG grid.
 ``--device_sampler`` decodes the whole grid in parallel through the
 HIP-graph decoder; with ``--fused`` a plain ``lstm`` or ``layer_norm``
 decoder of size 256 or 512 runs through its whole-sketch kernel
 (``sample.fused.fused_vae_decoder``) instead, and anything those do not take
-falls back to the graph decoder.
+falls back to the graph decoder. The two dataset modes run on the host
+sampler, the graph decoder (``--device_sampler``, on any device) and the
+whole-sketch kernels alike.
 """
 from __future__ import annotations
 
 import argparse
+import math
 import os
 import sys
 
@@ -31,7 +49,7 @@ def main(argv=None) -> int:
     p = argparse.ArgumentParser()
     p.add_argument("--save_dir", default="save/vae")
     p.add_argument("--out", default="vae_samples.svg")
-    p.add_argument("--mode", choices=["random", "class", "interpolate"], default="random")
+    p.add_argument("--mode", choices=["random", "class", "interpolate", "reconstruct", "complete"], default="random")
     p.add_argument("--n", type=int, default=10)
     p.add_argument("--label", type=int, default=0)
     p.add_argument("--temperature", type=float, default=0.5)
@@ -49,9 +67,24 @@ def main(argv=None) -> int:
                         "672 (2.7x at 128), slower at 1024. Measured on vae_layernorm: faster for --n 1, 128 (1.9x) "
                         "and 448 (1.05x), slower at 1024 (0.55x); one launch takes 224 rows at size 512 and larger "
                         "grids run as successive launches, so expect it to lose from 3 launches (--n > 448) on")
+    p.add_argument("--data", default=None, help="reconstruct / complete: sketch pack (.npz) with train/valid/test "
+                                                "splits")
+    p.add_argument("--synthetic", type=int, default=0, help="reconstruct / complete: synthetic corpus of this size")
+    p.add_argument("--split", choices=["test", "valid"], default="test")
+    p.add_argument("--offset", type=int, default=0, help="reconstruct / complete: index of the first sketch")
+    p.add_argument("--sample_z", action="store_true",
+                   help="encoded latents are mu + sigma * eps instead of mu")
+    p.add_argument("--prefix_frac", type=float, default=0.5,
+                   help="complete: the share of each sketch's strokes given to the decoder")
+    p.add_argument("--completions", type=int, default=1, help="complete: endings generated per prefix")
+    p.add_argument("--z_from", choices=["prefix", "full", "prior"], default="prefix",
+                   help="complete: latent of a conditional model (encode the prefix, the whole sketch, or draw it)")
     a = p.parse_args(argv)
     if a.fused and not a.device_sampler:
         p.error("--fused needs --device_sampler")
+    from_data = a.mode in ("reconstruct", "complete")
+    if a.mode == "complete" and (a.completions < 1 or not 0.0 <= a.prefix_frac <= 1.0):
+        p.error("--completions must be >= 1 and --prefix_frac in [0, 1]")
     import torch
     from ..ckpt import checkpoint as ckpt
     from ..config import load_json
@@ -72,31 +105,85 @@ def main(argv=None) -> int:
         z0, z1 = rng.randn(cfg.z_size), rng.randn(cfg.z_size)
         zs = np.stack([slerp(z0, z1, t) for t in np.linspace(0, 1, a.n)])
     labels = np.full(a.n, a.label if a.mode == "class" else 0)
+    N = cfg.max_seq_len
+    prefix = plen = shown = None      # complete: [rows, P, 5] stroke-5 prefixes and their lengths; shown: data sketches
+    group = 1                         # decoded sketches per shown one
+    if from_data:
+        from ..data.strokes import pad_batch_magenta
+        from .vae_eval import load_split
+        if a.mode == "reconstruct" and not cfg.conditional:
+            print("--mode reconstruct needs a conditional model (an encoder and a latent)", file=sys.stderr)
+            return 2
+        ds, _ = load_split(cfg, a.data, a.synthetic, a.split, a.save_dir)
+        if ds is None or len(ds) < a.offset + a.n or a.offset < 0:
+            print("the %s split has no sketches [%d, %d)" % (a.split, a.offset, a.offset + a.n), file=sys.stderr)
+            return 1
+        data = [np.asarray(x, np.float32) for x in ds.strokes[a.offset:a.offset + a.n]]
+        labels = np.asarray(ds.labels[a.offset:a.offset + a.n], dtype=np.int64)
+
+        def encode(sk):
+            """Latents of stroke-3 sketches: mu, or mu + sigma * eps with --sample_z."""
+            x = torch.as_tensor(pad_batch_magenta(sk, N), device=device)
+            lens = torch.as_tensor([len(x_) for x_ in sk], dtype=torch.int64, device=device)
+            with torch.no_grad():
+                mu, presig = (t.float().cpu().numpy() for t in model.encode(x, lens))
+            return mu + np.exp(presig / 2.0) * rng.randn(*mu.shape) if a.sample_z else mu
+
+        shown = data
+        if a.mode == "reconstruct":
+            zs = encode(data)
+        else:
+            group = a.completions
+            k = [min(int(math.ceil(a.prefix_frac * len(x))), len(x) - 1) for x in data]
+            shown = [x[:k_] for x, k_ in zip(data, k)]
+            P = max(max(k), 1)
+            pre = pad_batch_magenta(shown, P)[:, 1:]        # stroke-5 rows (no start token), padded past each length
+            if cfg.conditional and a.z_from != "prior":
+                # a prefix of no strokes has nothing to encode: its latent is the prior mean
+                src = data if a.z_from == "full" else [x if len(x) else np.zeros((1, 3), np.float32) for x in shown]
+                zs = encode(src)
+                if a.z_from == "prefix":
+                    zs[[i for i, k_ in enumerate(k) if k_ == 0]] = 0.0
+            zs = np.repeat(zs, group, axis=0)
+            if a.z_from == "prior":
+                zs = rng.randn(a.n * group, cfg.z_size)
+            labels = np.repeat(labels, group)
+            prefix, plen = np.repeat(pre, group, axis=0), np.repeat(np.asarray(k, np.int64), group)
+    rows = len(labels)
     sketches = []
     if a.fused and not device.startswith("cuda"):
         print("--fused: no GPU device, sampling on the host")
-    if a.device_sampler and device.startswith("cuda"):
+    if a.device_sampler and (device.startswith("cuda") or from_data):
         zt, lt = torch.as_tensor(zs, dtype=torch.float32, device=device), torch.as_tensor(labels, device=device)
+        pre_kw = {}
+        if prefix is not None:
+            pre_kw = dict(prefix=torch.as_tensor(prefix, device=device), prefix_len=torch.as_tensor(plen, device=device))
         s = None
+        if not device.startswith("cuda"):
+            a.fused = False
         if a.fused:
             from ..sample.fused import NotCoResident, fused_vae_decoder
             try:
-                s, _ = fused_vae_decoder(model, a.n, cfg.max_seq_len, a.temperature, a.greedy).run(
-                    seed=a.seed, z=zt, labels=lt)
+                s, _ = fused_vae_decoder(model, rows, cfg.max_seq_len, a.temperature, a.greedy).run(
+                    seed=a.seed, z=zt, labels=lt, **pre_kw)
             except ValueError:
                 print("--fused: needs an lstm or layer_norm decoder of size 256 (<= 32 mixtures) or 512 (<= 20); "
                       "using the graph decoder")
             except NotCoResident as e:
                 print("--fused: %s; using the graph decoder" % e)
         if s is None:
-            dec = GraphDecoder(model, a.n, cfg.max_seq_len, a.temperature, a.greedy, fp8=a.fp8)
-            s, _ = dec.run(seed=a.seed, z=zt, labels=lt)
+            dec = GraphDecoder(model, rows, cfg.max_seq_len, a.temperature, a.greedy, fp8=a.fp8)
+            s, _ = dec.run(seed=a.seed, z=zt, labels=lt, **pre_kw)
         sketches = [to_normal_strokes(x) for x in s.cpu().numpy()]
     else:
-        for k in range(a.n):
+        for k in range(rows):
             z = torch.as_tensor(zs[k:k + 1], dtype=torch.float32, device=device)
-            s5, _ = sample_vae(model, cfg.max_seq_len, a.temperature, a.greedy, z=z, label=int(labels[k]), rng=rng)
+            pre_k = None if prefix is None else prefix[k, :plen[k]]
+            s5, _ = sample_vae(model, cfg.max_seq_len, a.temperature, a.greedy, z=z, label=int(labels[k]), rng=rng,
+                               prefix=pre_k)
             sketches.append(to_normal_strokes(s5))
+    if shown is not None:       # each data sketch (or its prefix) followed by what was decoded from it
+        sketches = [x for i, d in enumerate(shown) for x in [d] + sketches[i * group:(i + 1) * group]]
     grid_strokes3(sketches, a.out)
     print("wrote %s (%d sketches)" % (a.out, len(sketches)))
     return 0

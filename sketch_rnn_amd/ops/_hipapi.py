@@ -352,6 +352,7 @@ class DecodeSample(C.Structure):
         ("seed", _p), ("step", _u32), ("row0", _i),
         ("out_row", _p), ("ld_out", _i64),
         ("done", _p),
+        ("forced", _p), ("ld_forced", _i64), ("nforced", _p),
     ]
 
 
@@ -395,6 +396,12 @@ class HipLib:
         lib.skr_mdn_sample_slabs.argtypes = [_p, _i64, _i, _i64, _p, _i, _i, _i, _f, _i, _i, _p, _u32, _i, _p, _i64,
                                              _p, _i64, _p, _p]
         lib.skr_mdn_sample_slabs.restype = _i
+        lib.skr_mdn_sample_forced.argtypes = [_p, _i64, _i, _i, _i, _f, _i, _i, _p, _u32, _p, _i64, _p, _i64, _p, _p,
+                                              _p, _i64, _p, _p]
+        lib.skr_mdn_sample_forced.restype = _i
+        lib.skr_mdn_sample_slabs_forced.argtypes = [_p, _i64, _i, _i64, _p, _i, _i, _i, _f, _i, _i, _p, _u32, _i, _p,
+                                                    _i64, _p, _i64, _p, _p, _i64, _p, _p]
+        lib.skr_mdn_sample_slabs_forced.restype = _i
         lib.skr_inproj_fwd.argtypes = [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]
         lib.skr_inproj_fwd.restype = _i
         lib.skr_inproj_bwd.argtypes = [_p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p]

@@ -408,17 +408,10 @@ class _FusedVAEBase:
         xin[0, :, 2] = 1.0                                          # start token
         nforced = None
         if prefix is not None:
-            prefix = prefix.to(dev, torch.float32)
+            from .sampler import check_prefix
+            prefix, plen = check_prefix(self._name + ".run", prefix, prefix_len, B, N, dev)
             P = prefix.shape[1]
-            plen = (torch.full((B,), P, dtype=torch.int64, device=dev) if prefix_len is None
-                    else torch.as_tensor(prefix_len).to(dev, torch.int64))
-            if prefix.shape[0] != B or prefix.shape[2] != 5 or plen.shape != (B,):
-                raise ValueError(self._name + ".run: prefix must be [B, P, 5] and prefix_len [B]")
-            if bool((plen < 0).any()) or bool((plen > min(P, N)).any()):
-                raise ValueError(self._name + ".run: prefix_len must lie in [0, min(P, steps)]")
             inside = torch.arange(P, device=dev)[None, :] < plen[:, None]
-            if bool((inside & (prefix[:, :, 4] > 0)).any()):
-                raise ValueError(self._name + ".run: a prefix ends its sketch (pen state 4) inside its length")
             Pn = min(P, N)
             xin[1:Pn + 1, :, :5] = (prefix[:, :Pn] * inside[:, :Pn, None]).transpose(0, 1)
             nforced = plen

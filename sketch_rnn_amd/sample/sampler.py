@@ -110,9 +110,12 @@ def _adjust_temp(pdf: np.ndarray, temp: float) -> np.ndarray:
 @torch.no_grad()
 def sample_vae(model, seq_len: int = 250, temperature: float = 1.0, greedy: bool = False,
                z: Optional[torch.Tensor] = None, label: Optional[int] = None,
-               rng: Optional[np.random.RandomState] = None, py_rng: Optional[_random.Random] = None):
+               rng: Optional[np.random.RandomState] = None, py_rng: Optional[_random.Random] = None,
+               prefix=None):
     """One sketch from the VAE decoder. Returns ``(strokes5 [seq_len, 5], params)``
-    in the magenta layout (convert with ``data.strokes.to_normal_strokes``)."""
+    in the magenta layout (convert with ``data.strokes.to_normal_strokes``).
+    ``prefix [P, 5]`` (P <= seq_len, no end-of-sketch row) completes a
+    sketch: it is fed as the first P strokes, then the decoder samples."""
     rng = rng or np.random.RandomState()
     py_rng = py_rng or _random.Random()
     cfg = model.cfg
@@ -125,9 +128,22 @@ def sample_vae(model, seq_len: int = 250, temperature: float = 1.0, greedy: bool
     prev_x = torch.tensor([[0.0, 0.0, 1.0, 0.0, 0.0]], device=dev)
     strokes = np.zeros((seq_len, 5), dtype=np.float32)
     params = []
+    P = 0
+    if prefix is not None:
+        prefix = np.asarray(prefix, dtype=np.float32)
+        if prefix.ndim != 2 or prefix.shape[1] != 5 or prefix.shape[0] > seq_len:
+            raise ValueError("sample_vae: prefix must be [P, 5] with P <= seq_len")
+        if (prefix[:, 4] > 0).any():
+            raise ValueError("sample_vae: a prefix ends its sketch (pen state 4) inside its length")
+        P = prefix.shape[0]
     for i in range(seq_len):
         zh, state = model.decode_step(prev_x, zc, state)
         pi, mu1, mu2, s1, s2, rho, pen, _ = (t[0].double().cpu().numpy() for t in M.mixture_coef(zh, cfg.num_mixture))
+        if i < P:      # a given stroke: no draw (the random streams advance only on sampled strokes)
+            strokes[i] = prefix[i]
+            params.append([pi, mu1, mu2, s1, s2, rho, pen])
+            prev_x = torch.as_tensor(prefix[i:i + 1], dtype=torch.float32, device=dev)
+            continue
         if greedy:
             idx, pidx = int(np.argmax(pi)), int(np.argmax(pen))
             x1, x2 = mu1[idx], mu2[idx]
@@ -154,12 +170,42 @@ _SAMPLE_STREAM = 0x5A3D
 STEP_DECODER = os.environ.get("SKR_STEP_DECODER", "1") != "0"
 
 
+def check_prefix(name: str, prefix: torch.Tensor, prefix_len, B: int, N: int, dev):
+    """Validate the stroke prefixes of a ``run(prefix=, prefix_len=)`` call
+    (shared by :class:`GraphDecoder` and the whole-sketch decoders of
+    :mod:`.fused`): ``prefix [B, P, 5]``, ``prefix_len [B]`` in
+    ``[0, min(P, steps)]`` (default P), no end-of-sketch pen state inside a
+    row's length. Returns ``(prefix fp32, prefix_len int64)`` on ``dev``;
+    raises ``ValueError`` in ``name``'s name."""
+    prefix = torch.as_tensor(prefix).to(dev, torch.float32)
+    if prefix.dim() != 3:
+        raise ValueError(name + ": prefix must be [B, P, 5] and prefix_len [B]")
+    P = prefix.shape[1]
+    plen = (torch.full((B,), P, dtype=torch.int64, device=dev) if prefix_len is None
+            else torch.as_tensor(prefix_len).to(dev, torch.int64))
+    if prefix.shape[0] != B or prefix.shape[2] != 5 or plen.shape != (B,):
+        raise ValueError(name + ": prefix must be [B, P, 5] and prefix_len [B]")
+    if bool((plen < 0).any()) or bool((plen > min(P, N)).any()):
+        raise ValueError(name + ": prefix_len must lie in [0, min(P, steps)]")
+    inside = torch.arange(P, device=dev)[None, :] < plen[:, None]
+    if bool((inside & (prefix[:, :, 4] > 0)).any()):
+        raise ValueError(name + ": a prefix ends its sketch (pen state 4) inside its length")
+    return prefix, plen
+
+
 def mdn_sample_torch(zh: torch.Tensor, M_: int, mode: int, temp: float, greedy: bool, fix_pen: bool,
                      seed, step: int, out_row: torch.Tensor, next_x: torch.Tensor, done: torch.Tensor,
-                     params: Optional[torch.Tensor] = None) -> None:
+                     params: Optional[torch.Tensor] = None, forced: Optional[torch.Tensor] = None,
+                     nforced: Optional[torch.Tensor] = None) -> None:
     """PyTorch transcription of ``csrc/sampler.hip`` (same hash random
     numbers, same draws): the CPU path of :class:`GraphDecoder` and the
-    oracle the kernel is tested against."""
+    oracle the kernel is tested against.
+
+    ``forced [B, 5]`` with ``nforced [B]``: a row with ``step < nforced[b]``
+    emits ``forced[b]`` bit for bit instead of its draw, as ``out_row`` and as
+    ``next_x``, takes its finished state from that row's stop column and
+    never emits padding (``csrc/mdn_sample.h``). ``params`` keeps describing
+    the draw."""
     from ..models.cells import hash_uniform
     B = zh.shape[0]
     z = zh.float()
@@ -196,18 +242,33 @@ def mdn_sample_torch(zh: torch.Tensor, M_: int, mode: int, temp: float, greedy: 
     stop_col = 4 if mode == 1 else 3
     pad = torch.zeros(B, 5, device=z.device)
     pad[:, stop_col] = 1.0
-    out_row.copy_(torch.where((done != 0).unsqueeze(-1), pad, row))
+    stop = pidx + 2 == stop_col
+    emit = torch.where((done != 0).unsqueeze(-1), pad, row)
+    if nforced is not None:    # a select: nothing of the draw (NaN included) reaches a forced row
+        on = step < nforced.to(z.device).long()
+        fr = forced.to(z.device, torch.float32)
+        row = torch.where(on.unsqueeze(-1), fr, row)
+        emit = torch.where(on.unsqueeze(-1), fr, emit)
+        stop = torch.where(on, fr[:, stop_col] > 0, stop)
+    out_row.copy_(emit)
     next_x.copy_(row)
-    done.copy_(torch.where(pidx + 2 == stop_col, torch.ones_like(done), done))
+    done.copy_(torch.where(stop, torch.ones_like(done), done))
     if params is not None:
         params.copy_(torch.stack([idx.float(), pidx.float(), s1, s2], -1))
 
 
 def mdn_sample_device(zh: torch.Tensor, M_: int, mode: int, temp: float, greedy: bool, fix_pen: bool,
                       seed: torch.Tensor, step: int, out_row: torch.Tensor, next_x: torch.Tensor,
-                      done: torch.Tensor, params: Optional[torch.Tensor] = None) -> None:
+                      done: torch.Tensor, params: Optional[torch.Tensor] = None,
+                      forced: Optional[torch.Tensor] = None, nforced: Optional[torch.Tensor] = None) -> None:
+    """``csrc/sampler.hip`` on a GPU tensor, :func:`mdn_sample_torch` elsewhere.
+    ``forced [B, 5]`` (any row stride) with ``nforced [B]`` int32: rows with
+    ``step < nforced[b]`` emit ``forced[b]`` instead of their draw."""
+    if (forced is None) != (nforced is None):
+        raise ValueError("mdn_sample_device: forced and nforced go together")
     if zh.device.type != "cuda":
-        return mdn_sample_torch(zh, M_, mode, temp, greedy, fix_pen, seed, step, out_row, next_x, done, params)
+        return mdn_sample_torch(zh, M_, mode, temp, greedy, fix_pen, seed, step, out_row, next_x, done, params,
+                                forced, nforced)
     assert zh.dtype == torch.float32 and zh.stride(1) == 1 and zh.shape[1] >= 3 + 6 * M_
     assert out_row.dtype == torch.float32 and out_row.stride(-1) == 1 and out_row.shape[0] == zh.shape[0]
     assert next_x.shape == (zh.shape[0], 5) and next_x.stride(-1) == 1
@@ -215,6 +276,18 @@ def mdn_sample_device(zh: torch.Tensor, M_: int, mode: int, temp: float, greedy:
     from ..utils import native
     lib = native.require_hip()
     import ctypes
+    if nforced is not None:
+        B = zh.shape[0]
+        assert forced.dtype == torch.float32 and forced.shape == (B, 5) and forced.stride(1) == 1
+        assert nforced.dtype == torch.int32 and nforced.shape == (B,) and nforced.stride(0) == 1
+        rc = lib.lib.skr_mdn_sample_forced(
+            zh.data_ptr(), zh.stride(0), B, M_, mode, temp, int(greedy), int(fix_pen), seed.data_ptr(), step,
+            out_row.data_ptr(), out_row.stride(0), next_x.data_ptr(), next_x.stride(0), done.data_ptr(),
+            params.data_ptr() if params is not None else None, forced.data_ptr(), forced.stride(0),
+            nforced.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            raise RuntimeError("skr_mdn_sample_forced failed (%d)" % rc)
+        return
     rc = lib.lib.skr_mdn_sample(ctypes.c_void_p(zh.data_ptr()), ctypes.c_int64(zh.stride(0)), ctypes.c_int(zh.shape[0]),
                                 ctypes.c_int(M_), ctypes.c_int(mode), ctypes.c_float(temp), ctypes.c_int(int(greedy)),
                                 ctypes.c_int(int(fix_pen)), ctypes.c_void_p(seed.data_ptr()), ctypes.c_uint32(step),
@@ -269,6 +342,10 @@ class GraphDecoder:
             self.x0[:, 2] = 1.0
             self.z = torch.zeros(batch, max(cfg.z_size, 1), device=dev)
             self.labels = torch.zeros(batch, dtype=torch.int64, device=dev)
+            # stroke prefixes (sketch completion): static, so the captured graphs always carry them and a
+            # prefix never causes a recapture; nforced all zero = a plain decode
+            self.prefix = torch.zeros(batch, steps, 5, device=dev)
+            self.nforced = torch.zeros(batch, dtype=torch.int32, device=dev)
         self.graphs = None
         self.use_graph = use_graph and dev.type == "cuda"
         c = int(chunk or self.CHUNK)
@@ -313,7 +390,7 @@ class GraphDecoder:
         lib = native.require_hip().lib
         model, B, N = self.model, self.B, self.N
         cfg = model.cfg
-        ld_out = self.out.stride(0)
+        ld_out, ld_pre = self.out.stride(0), self.prefix.stride(0)
         main = torch.cuda.current_stream(self.dev)
         stp = [(r0, n, st, main if stream is None else stream) for r0, n, st, stream in stp]
         cy = self._carry
@@ -338,17 +415,19 @@ class GraphDecoder:
                     for t in range(t0, t1):
                         smp = None if t == 0 else st.sample_args(
                             t - 1, r0, self.out[r0:r0 + n, t - 1], done, self.seed, self.Mx, self.mode, self.temp,
-                            self.greedy, self.fix_pen)
+                            self.greedy, self.fix_pen, forced=self.prefix[r0:r0 + n, t - 1],
+                            nforced=self.nforced[r0:r0 + n])
                         st.step_fused(t, smp)
                     if t1 == N:
                         st.head()          # the last stroke: head + sampler
-                        rc = lib.skr_mdn_sample_slabs(
+                        rc = lib.skr_mdn_sample_slabs_forced(
                             st.ZS.data_ptr(), 128, st.S_o, n * 128, st._w["bo"].data_ptr(), n, self.Mx, self.mode,
                             self.temp, int(self.greedy), int(self.fix_pen), self.seed.data_ptr(), N - 1, r0,
                             self.out[r0, N - 1].data_ptr(), ld_out, st.X.data_ptr(), 5, done.data_ptr(),
+                            self.prefix[r0, N - 1].data_ptr(), ld_pre, self.nforced[r0:].data_ptr(),
                             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
                         if rc != 0:
-                            raise RuntimeError("skr_mdn_sample_slabs failed (%d)" % rc)
+                            raise RuntimeError("skr_mdn_sample_slabs_forced failed (%d)" % rc)
                 continue
             with torch.cuda.stream(stream):
                 if t0 == 0:
@@ -359,13 +438,14 @@ class GraphDecoder:
                     nx = torch.empty(n, 5, device=self.dev)
 
                     def sample(zs, ldz, nslab, slab, bias, r0=r0, n=n, t=t, nx=nx):
-                        rc = lib.skr_mdn_sample_slabs(
+                        rc = lib.skr_mdn_sample_slabs_forced(
                             zs.data_ptr(), ldz, nslab, slab, bias.data_ptr(), n, self.Mx, self.mode, self.temp,
                             int(self.greedy), int(self.fix_pen), self.seed.data_ptr(), t, r0,
                             self.out[r0, t].data_ptr(), ld_out, nx.data_ptr(), 5, self.done[r0:].data_ptr(),
+                            self.prefix[r0, t].data_ptr(), ld_pre, self.nforced[r0:].data_ptr(),
                             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
                         if rc != 0:
-                            raise RuntimeError("skr_mdn_sample_slabs failed (%d)" % rc)
+                            raise RuntimeError("skr_mdn_sample_slabs_forced failed (%d)" % rc)
                     st.step(x, t, sample)
                     x = nx
                 cy["x%d" % i] = x
@@ -405,8 +485,9 @@ class GraphDecoder:
             else:
                 zh, state = model.step(x, state)
             nx = torch.empty(B, 5, device=self.dev)
+            forced = (self.prefix[:, t], self.nforced) if self.kind == "vae" else (None, None)
             mdn_sample_device(zh.contiguous(), self.Mx, self.mode, self.temp, self.greedy, self.fix_pen, self.seed, t,
-                              self.out[:, t], nx, self.done)
+                              self.out[:, t], nx, self.done, None, *forced)
             x = nx
         cy["x"], cy["state"] = x, state
 
@@ -420,7 +501,28 @@ class GraphDecoder:
             self.out[:, t:, 4 if self.kind == "vae" else 3] = 1.0
 
     @torch.no_grad()
-    def run(self, seed: int = 0, z: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None):
+    def run(self, seed: int = 0, z: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
+            prefix: Optional[torch.Tensor] = None, prefix_len: Optional[torch.Tensor] = None):
+        """Returns ``(strokes [B, N, 5], lengths [B])``.
+
+        ``prefix [B, P, 5]`` with ``prefix_len [B]`` (default P for every row;
+        VAE models only) completes sketches: stroke t of row b is
+        ``prefix[b, t]`` for ``t < prefix_len[b]`` and the decoder continues
+        from there (the contract of the whole-sketch decoders in
+        :mod:`.fused`). The prefix is copied into static buffers the captured
+        graphs read, so it never causes a recapture, and a later run without
+        one is a plain decode."""
+        if prefix is not None or prefix_len is not None:
+            if self.kind != "vae":
+                raise ValueError("GraphDecoder.run: stroke prefixes need a VAE model")
+            if prefix is None:
+                raise ValueError("GraphDecoder.run: prefix_len without a prefix")
+            prefix, plen = check_prefix("GraphDecoder.run", prefix, prefix_len, self.B, self.N, self.dev)
+            Pn = min(prefix.shape[1], self.N)
+            self.prefix[:, :Pn].copy_(prefix[:, :Pn])
+            self.nforced.copy_(plen)
+        elif self.kind == "vae":
+            self.nforced.zero_()
         if z is not None:
             self.z.copy_(z)
         elif self.kind == "vae":
