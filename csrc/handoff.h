@@ -13,8 +13,8 @@
 #pragma once
 #include "common.h"
 
-// Per-launch state of a chained launch (csrc/chain_step.hip, csrc/hyper_mod.hip;
-// mirrored by sketch_rnn_amd/ops/_hipapi.py ChainSync).
+// Per-launch state of a chained launch (csrc/chain_step.hip; mirrored by
+// sketch_rnn_amd/ops/_hipapi.py ChainSync).
 struct ChainSync {
     uint32_t* counters;   // [n] rotating arrival counters of this launch kind (zeroed once)
     int n, k;             // this launch uses counters[k] and zeroes counters[(k + 1) % n]
@@ -100,14 +100,12 @@ __device__ __forceinline__ void chain_arrive(uint32_t* counter) {
     if (threadIdx.x == 0) __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// SLEEP: s_sleep units (64 clocks each) between polls -- a longer period
-// puts fewer poll requests beside the streams of the workgroups that are
-// still producing (128 tiles polling one word every 64 clocks measurably
-// slowed a chained launch's rows: scripts/micro/chain3_probe.py).
-template <int SLEEP = 1>
+// One s_sleep unit (64 clocks) between polls: only cell rows wait here, a few
+// microseconds each. (128 GEMM tiles polling one word at that rate measurably
+// slowed the workgroups still producing: profiles/r6/chain3_probe.jsonl.)
 __device__ inline void chain_wait(const uint32_t* counter, uint32_t target, int* err) {
     if (threadIdx.x == 0) {
-        for (unsigned spins = 0;; spins += SLEEP) {
+        for (unsigned spins = 0;; ++spins) {
             if (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= target) break;
             if ((spins & 255) == 255) {
                 if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
@@ -116,7 +114,7 @@ __device__ inline void chain_wait(const uint32_t* counter, uint32_t target, int*
                     break;
                 }
             }
-            __builtin_amdgcn_s_sleep(SLEEP);
+            __builtin_amdgcn_s_sleep(1);
         }
     }
     // compiler barrier + workgroup barrier: no wave's slab loads move above the poll

@@ -133,17 +133,13 @@ __device__ __forceinline__ void row_exchange(float (&v)[N], float* mine, float* 
 // CHAIN (csrc/chain_step.hip, MOD 0): the R slabs are produced by tiles of
 // the SAME launch -- every other load is issued first, then the row waits on
 // the launch's arrival counter and reads the slabs with sc1 loads.
-// HSC1 (csrc/hyper_mod.hip hyper_cell_mod): the bf16 next-step operand h_lp
-// is read by workgroups of the SAME launch after the row's arrival, so it is
-// stored write-through (8-byte relaxed agent-scope stores, lp_kind 1 only).
-template <int NT, int V, int MOD, int DS, bool CHAIN = false, bool HSC1 = false>
+template <int NT, int V, int MOD, int DS, bool CHAIN = false>
 __device__ __forceinline__ void row_fwd_body(const FwdArgs& a, const int b, const uint32_t* chain_cnt = nullptr,
-                                             uint32_t chain_target = 0, int* chain_err = nullptr, const int tid0 = 0) {
+                                             uint32_t chain_target = 0, int* chain_err = nullptr) {
     static_assert(!CHAIN || (V == 4 && MOD == 0), "chained forward row: MOD 0, 16-byte slab loads");
-    static_assert(!HSC1 || V == 4, "write-through h_lp: 8-byte stores");
     constexpr int NW = NT / 64;
     __shared__ float lds[NW * 8];
-    const int tid = threadIdx.x - tid0, H = a.H, u0 = tid * V;   // tid0: first thread of the row (one-wave rows)
+    const int tid = threadIdx.x, H = a.H, u0 = tid * V;
     const int grp = a.grp_rows > 0 ? b / a.grp_rows : 0;
     const float* ln_g = a.ln_g + grp * 4 * H;
     const float* ln_b = a.ln_b + grp * 4 * H;
@@ -172,7 +168,7 @@ __device__ __forceinline__ void row_fwd_body(const FwdArgs& a, const int b, cons
     ldf<V>(a.lnc_g + grp * H + u0, lcg);
     ldf<V>(a.lnc_b + grp * H + u0, lcb);
     if constexpr (CHAIN) {
-        chain_wait<1>(chain_cnt, chain_target, chain_err);
+        chain_wait(chain_cnt, chain_target, chain_err);
         const __amdgpu_buffer_rsrc_t r = rsrc(a.R, 0x7fffffff);
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -267,11 +263,7 @@ __device__ __forceinline__ void row_fwd_body(const FwdArgs& a, const int b, cons
     if (a.h_carry != nullptr) stf<V>(a.h_carry + ro, h);
     if (a.c_out != nullptr) stf<V>(a.c_out + ro, cn);
     stf<V>(a.c_carry + ro, cn);
-    if constexpr (HSC1) {
-        const uint64_t w = (uint64_t)pack2(h[0], h[1]) | ((uint64_t)pack2(h[2], h[3]) << 32);
-        __hip_atomic_store((uint64_t*)((__hip_bfloat16*)a.h_lp + b * a.ld_lp + u0), w, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    } else if (a.lp_kind == 1) {
+    if (a.lp_kind == 1) {
         stb<V>((__hip_bfloat16*)a.h_lp + b * a.ld_lp + u0, h);
     } else {
         stf<V>((float*)a.h_lp + b * a.ld_lp + u0, h);
@@ -287,21 +279,11 @@ __device__ __forceinline__ void row_fwd_body(const FwdArgs& a, const int b, cons
 // the SAME launch -- every other load is issued first, then the row waits on
 // the launch's arrival counter and reads them with sc1 loads (16-byte
 // buffer loads); the arithmetic is unchanged.
-// DVSC1 (csrc/chain_step.hip, three-stage launch): dvec is read by GEMM tiles
-// of the SAME launch after the rows' arrival counter, so its stores are
-// write-through (sc1, 8-byte relaxed agent-scope atomic stores).
-template <int V>
-__device__ __forceinline__ void stb_sc1(void* p, const float (&v)[V]) {
-    static_assert(V == 4, "8-byte sc1 stores");
-    const uint64_t w = (uint64_t)pack2(v[0], v[1]) | ((uint64_t)pack2(v[2], v[3]) << 32);
-    __hip_atomic_store((uint64_t*)p, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // CL > 1: the row is split over CL workgroups (part c of CL owns units
 // [c H / CL, (c + 1) H / CL), NT V == H / CL), and its two LayerNorm-backward
 // row sums are exchanged between them in-launch as tagged granules
 // (cluster_allgather, csrc/cell_fwd_body.h; a.part / a.err, tag = step + 1).
-template <int NT, int V, bool MOD, int DO, bool CHAIN = false, bool DVSC1 = false, int CL = 1>
+template <int NT, int V, bool MOD, int DO, bool CHAIN = false, int CL = 1>
 __device__ __forceinline__ void row_bwd_body(const BwdArgs& a, const int b, const uint32_t* chain_cnt = nullptr,
                                              uint32_t chain_target = 0, int* chain_err = nullptr, const int c = 0) {
     static_assert(!CHAIN || V == 4, "chained row: 16-byte slab loads");
@@ -348,7 +330,7 @@ __device__ __forceinline__ void row_bwd_body(const BwdArgs& a, const int b, cons
         }
     }
     if constexpr (CHAIN) {
-        chain_wait<1>(chain_cnt, chain_target, chain_err);
+        chain_wait(chain_cnt, chain_target, chain_err);
         if (n1) {
             const __amdgpu_buffer_rsrc_t r = rsrc(a.dh_rec, 0x7fffffff);
             const int64_t base = (int64_t)b * a.ld_dh_rec + u0;
@@ -459,17 +441,11 @@ __device__ __forceinline__ void row_bwd_body(const BwdArgs& a, const int b, cons
             stb<V>((__hip_bfloat16*)a.dxp + b * a.ld_dxp + q * H + u0, t);
 #pragma unroll
             for (int j = 0; j < V; ++j) t[j] = dg[q][j] * xv[q][j];
-            if constexpr (DVSC1) stb_sc1<V>((__hip_bfloat16*)a.dvec + q * a.vec_gs + o0, t);
-            else stb<V>((__hip_bfloat16*)a.dvec + q * a.vec_gs + o0, t);
+            stb<V>((__hip_bfloat16*)a.dvec + q * a.vec_gs + o0, t);
 #pragma unroll
             for (int j = 0; j < V; ++j) t[j] = dg[q][j] * rv[q][j];
-            if constexpr (DVSC1) {
-                stb_sc1<V>((__hip_bfloat16*)a.dvec + (4 + q) * a.vec_gs + o0, t);
-                stb_sc1<V>((__hip_bfloat16*)a.dvec + (8 + q) * a.vec_gs + o0, dg[q]);
-            } else {
-                stb<V>((__hip_bfloat16*)a.dvec + (4 + q) * a.vec_gs + o0, t);
-                stb<V>((__hip_bfloat16*)a.dvec + (8 + q) * a.vec_gs + o0, dg[q]);
-            }
+            stb<V>((__hip_bfloat16*)a.dvec + (4 + q) * a.vec_gs + o0, t);
+            stb<V>((__hip_bfloat16*)a.dvec + (8 + q) * a.vec_gs + o0, dg[q]);
 #pragma unroll
             for (int j = 0; j < V; ++j) dr[j] = dg[q][j] * ah[q][j];
         } else {

@@ -463,9 +463,6 @@ class HipLib:
         lib.skr_chain_ln_bwd.argtypes = [C.POINTER(GemmProblem), _i, C.POINTER(LstmBwdArgs), C.POINTER(ChainSync), _p]
         lib.skr_chain_ln_bwd.restype = _i
         lib.skr_chain_bwd_main.restype = _i
-        lib.skr_chain_bwd_main3.argtypes = [C.POINTER(GemmProblem), _i, C.POINTER(GemmProblem), C.POINTER(LstmBwdArgs),
-                                            C.POINTER(ChainSync), C.POINTER(ChainSync), _p]
-        lib.skr_chain_bwd_main3.restype = _i
         lib.skr_mx8_quant_t.argtypes = [_p, _i64, _i, _i, _p, _p, _p]
         lib.skr_mx8_quant_t.restype = _i
         lib.skr_mx8_quant_rows.argtypes = [_p, _i64, _i, _i, _i, _p, _i64, _p, _p]
@@ -474,8 +471,6 @@ class HipLib:
         lib.skr_mx8_gemm.restype = _i
         lib.skr_mx8_set_layout.argtypes = [_i]
         lib.skr_mx8_set_layout.restype = _i
-        lib.skr_chain3_set_probe.argtypes = [_i]
-        lib.skr_chain3_set_probe.restype = _i
         lib.skr_lstm_fused_fwd.argtypes = [C.POINTER(FusedFwdArgs), _p]
         lib.skr_lstm_fused_fwd.restype = _i
         lib.skr_lstm_fused_bwd.argtypes = [C.POINTER(FusedBwdArgs), _p]
@@ -503,9 +498,6 @@ class HipLib:
         lib.skr_hyper_mod_fwd.argtypes = [_p, _i64, _p, _p, _p, _p, _i64, _i, _p, _p, _p, _p, _i, _i, _i,
                                           C.POINTER(ModDecode), _p]
         lib.skr_hyper_mod_fwd.restype = _i
-        lib.skr_hyper_cell_mod.argtypes = [C.POINTER(LstmFwdArgs), _p, _p, _p, _i, _p, _i64, _i, _p, _p, _p, _p, _i,
-                                           C.POINTER(ChainSync), _p]
-        lib.skr_hyper_cell_mod.restype = _i
         lib.skr_cast_transpose_bf16.argtypes = [_p, _i64, _i64, _i, _i, _i, _p, _i64, _i64, _p, _i64, _i64, _p]
         lib.skr_cast_transpose_bf16.restype = _i
         lib.skr_hash_normal.argtypes = [_p, _u32, _u32, _p, _i64, _p]

@@ -47,20 +47,10 @@ HYPER_BWD_FUSE = True
 # launches per backward step instead of four. SKR_CHAIN=0 keeps the unchained
 # launches (A/B).
 CHAIN = os.environ.get("SKR_CHAIN", "1") != "0"
-# Three-stage chained launch (csrc/chain_step.hip skr_chain_bwd_main3): the
-# dvec P^T product of step t joins the chained launch too -- producer
-# workgroups that finished their dR_hyp W_y^T tile stage their P^T slice in
-# LDS while the main-cell rows compute, then run the tile on the rows' arrival
-# counter: two launches per backward step instead of three. Bit-identical to
-# the separate launch, but OFF: measured (profiles/r6/chain3_probe.jsonl, B =
-# 100) 60.8 us per backward step against 50.9 for two-stage chain + separate
-# launch. Producers that stay resident waiting on the rows cost 7.4 us by
-# themselves (probe 3: no staging, no tile), and the tile tail -- 154 KB of
-# dvec per workgroup through sc1 loads from the fabric -- another ~10 us,
-# more than the 8 us launch it replaces. It also needs at least as many
-# producer tiles as dvec P^T tail tiles: at SAY_CAP = 2 (below) the launch
-# declines and the two-stage chain runs (the bitwise test pins SAY_CAP = 4).
-CHAIN3 = False
+# (Round 6 measured the dvec P^T product of step t as a third stage of the
+# chained launch, run from LDS by producer workgroups that had finished their
+# tile, at 31.14 vs 24.0 ms/step: profiles/r6/chain3_ab_v1.log, probes in
+# profiles/r6/chain3_probe.jsonl; removed, its code is last in commit c0b29ff.)
 # Workgroups per main-cell row in the chained backward launch (1 or 2): 2
 # splits each row's ~300 KB of loads over two CUs and exchanges the two
 # LayerNorm-backward row sums in-launch (csrc/chain_step.hip CL). Tested,
@@ -78,18 +68,10 @@ CHAIN_CL = 1
 # Debug (tests): NaN-fill the d[h | hh] slabs before every chained launch, so
 # a main-cell row that read them ahead of its producer tiles shows up as NaN.
 CHAIN_POISON = False
-# Hyper cell + modulation step in ONE forward launch (csrc/hyper_mod.hip
-# hyper_cell_mod): wave 0 of modulation workgroup b runs the hyper cell of row
-# b and publishes its hh row; every modulation tile fetches its P fragments,
-# x-projection and R slabs while the rows compute, then waits for all rows
-# (timing probes: the P fetch is 4.8 of the separate modulation launch's
-# 10.9 us). 65 <= B <= 128. OFF: measured 28.2 us per launch against 4.9 + 10.9
-# for the pair, vae_large 26.2 vs 23.65 ms/step (profiles/r6/cm2/): the
-# one-wave hyper cell row takes ~11 us inside the launch (probes: no wait
-# 24.9, no rows 13.5 us).
-CELL_MOD = False
-CELL_MOD_POISON = False   # tests: NaN-fill the hh rows before each such launch
-CELL_MOD_STATS = {"launches": 0}
+# (Round 6 measured the hyper cell rows inside the modulation launch -- a
+# seventh wave per workgroup ran one row and published hh, the tiles fetched
+# their other operands and waited -- at 26.2 vs 23.65 ms/step on vae_large:
+# profiles/r6/cm2/; removed, its code is last in commit c0b29ff.)
 # The main input projection x W_x + z W_z ([T, B, 4H], the largest tensor the
 # forward writes) stored in bf16 on the fused-modulation path; False keeps it
 # fp32 (A/B, scripts/micro/xh_ab.py).
@@ -374,8 +356,6 @@ class _HyperSeq(torch.autograd.Function):
         am.forget_bias, am.keep = float(forget_bias), float(keep)
         am.seed, am.stream = sd.data_ptr(), int(stream)
         am.ld_lp, am.lp_kind = K, _lp_kind(A)
-        cell_mod = CELL_MOD and hmod and 65 <= B <= 128 and T >= 2 and Hh == 256 and _lp_kind(A) == 1
-        cmc = gemm.ChainCounters(dev, "hyp_cell_mod", T) if cell_mod else None
         clm = _ClusterSync(T, B, H, dev, ln=mln_on, C=HYPER_MAIN_C if hmod else 0)
         clh = _ClusterSync(T, B, Hh, dev)
         st = _stream()
@@ -401,8 +381,7 @@ class _HyperSeq(torch.autograd.Function):
             else:
                 rgemm(A[t, :, :H], WhT, RM[rmi(t)], S_m)
                 rgemm(A[t], WyT, RY, S_y)
-            if not cell_mod:
-                _cell_fwd(lib, ah, True, 0, st, "hyper_fwd_step")
+            _cell_fwd(lib, ah, True, 0, st, "hyper_fwd_step")
             am.xp, am.R, am.vec = XH[t].data_ptr(), RM[rmi(t)].data_ptr(), VEC[t].data_ptr()
             am.r_lp = RLP[t].data_ptr() if (RLP is not None and not hmod) else None
             am.c_prev, am.step = (c0c if t == 0 else CC[t]).data_ptr(), t
@@ -411,23 +390,6 @@ class _HyperSeq(torch.autograd.Function):
             am.h_lp, am.c_carry = A[t + 1, :, :H].data_ptr(), CC[t + 1].data_ptr()
             if hmod:
                 am.gpre, am.gstats, am.gstat_tiles = GP.data_ptr(), GS.data_ptr(), H // 32
-            if cell_mod:   # hyper cell rows + modulation tiles, one launch
-                if CELL_MOD_POISON:
-                    A[t + 1, :, H:].fill_(float("nan"))
-                rc = lib.lib.skr_hyper_cell_mod(ctypes.byref(ah), PlT.data_ptr(), qb.data_ptr(), XHc[t].data_ptr(),
-                                                xh_dec.xh_bf16, RM[rmi(t)].data_ptr(), B * G, S_m, VEC[t].data_ptr(),
-                                                GP.data_ptr(), _ptr(RLP[t] if RLP is not None else None),
-                                                GS.data_ptr(), H, ctypes.byref(cmc.at(t)), st)
-                if rc == 0:
-                    CELL_MOD_STATS["launches"] += 1
-                    _cell_fwd(lib, am, mln_on, mod, st, "hyper_main_fwd_step")
-                    continue
-                if rc not in (-2, -3, -4):
-                    _check(rc, "hyper_cell_mod")
-                # not taken: the two launches from here on (counters cleared for the next sequence)
-                cell_mod = False
-                cmc.buf.zero_()
-                _cell_fwd(lib, ah, True, 0, st, "hyper_fwd_step")
             if hmod:
                 apply_hm_zgrid(lib)
                 _check(lib.lib.skr_hyper_mod_fwd(A[t + 1, :, H:].data_ptr(), K, PlT.data_ptr(), qb.data_ptr(),
@@ -550,12 +512,8 @@ class _HyperSeq(torch.autograd.Function):
         chain_m = CHAIN and lp_on and dev.type == "cuda" and T >= 3 and H == 2048 and s.mln_on and \
             s.VEC.dtype == torch.bfloat16 and s.RLP is not None and dHout is not None and S_ay <= 8
         cm = gemm.ChainCounters(dev, "hyp_bwd_m", T - 1) if chain_m else None
-        # three-stage launches (CHAIN3): dvec P^T inside the chained launch, on
-        # the rows' own rotating counters; the bf16 fused-order backward only
-        chain3 = chain_m and CHAIN3 and bfuse
-        if chain_m and CHAIN_CL == 2 and not chain3:   # two workgroups per chained row (exchange buffer C = 2)
+        if chain_m and CHAIN_CL == 2:   # two workgroups per chained row (exchange buffer C = 2)
             clm = _ClusterSync(T, B, H, dev, ln=s.mln_on, C=2)
-        cm3 = gemm.ChainCounters(dev, "hyp_bwd_m3", T - 1) if chain3 else None
         # weight gradients beside the scan (BG_WGRAD): destinations allocated
         # here, on the scan's stream; chunks [t, hi) issued as the scan passes t
         A2 = s.A[:T].reshape(TB, K)
@@ -601,21 +559,11 @@ class _HyperSeq(torch.autograd.Function):
             am.dG = None if lp_on else dRM[t].data_ptr()
             am.dG_lp = dRM_lp[t].data_ptr() if lp_on else None
             am.dxp, am.dvec = dXH[t].data_ptr(), dVEC[t].data_ptr()
-            ran = ran3 = False
+            ran = False
             if chain_m and t < T - 1:   # dR_hyp W_y^T of step t + 1 -> this main cell, one launch
                 if CHAIN_POISON:
                     DAY.fill_(float("nan"))
-                    if chain3:
-                        dVEC[t].fill_(float("nan"))
-                if chain3:   # ... -> dvec P^T of this step, the same launch
-                    ran3 = gemm.chain_bwd_main3([(dRY_lp[t + 1], s.Wyl, DAY, S_ay)], (dVEC[t], s.Pl, DHZ, S_h), am,
-                                                cm.at(T - 2 - t), cm3.at(T - 2 - t)) == 0
-                    if not ran3:
-                        chain3 = False
-                        cm3.buf.zero_()
-                    ran = ran3
-                if not ran:
-                    ran = gemm.chain_bwd_main([(dRY_lp[t + 1], s.Wyl, DAY, S_ay)], am, cm.at(T - 2 - t)) == 0
+                ran = gemm.chain_bwd_main([(dRY_lp[t + 1], s.Wyl, DAY, S_ay)], am, cm.at(T - 2 - t)) == 0
                 if not ran:   # shape not taken by the chained row: unchained launches from here on
                     chain_m = False
                     # launches 0 .. k-1 left counts in their counters (only launch
@@ -624,7 +572,6 @@ class _HyperSeq(torch.autograd.Function):
                     gemm.rec_gemm(dRY_lp[t + 1], s.Wyl, DAY, S_ay)
                 else:
                     ROW_STATS["chain"] += 1
-                    ROW_STATS["chain3"] += int(ran3)
             if not ran:
                 _cell_bwd(lib, am, s.mln_on, 2 if s.VEC.dtype == torch.bfloat16 else 1, st, "hyper_main_bwd_step")
             ah.c_prev = (s.hc0 if t == 0 else s.HCC[t]).data_ptr()
@@ -634,8 +581,7 @@ class _HyperSeq(torch.autograd.Function):
             ah.dG_lp = dRY_lp[t].data_ptr() if lp_on else None
             ah.dlny, ah.dlncy = HDLNY[t].data_ptr(), HDLNCY[t].data_ptr()
             if bfuse:   # dvec P^T, then the hyper cell beside dR_main W_h^T (one launch)
-                if not ran3:   # (chained: ran in the launch above)
-                    gemm.rec_gemm(dVEC[t], s.Pl, DHZ, S_h)
+                gemm.rec_gemm(dVEC[t], s.Pl, DHZ, S_h)
                 gemm.rec_gemm_group_cellbwd([(dRM_lp[t], s.Whl, DAM, S_am)], ah)
                 ROW_STATS["cluster"] += 1   # (the clustered cell body, C = 1)
             else:

@@ -1278,77 +1278,6 @@ def test_hyper_chained_launches_vs_unchained(B, T, fin_w):
         assert e_c <= 1.5 * e_p + 1e-3 * scale, (n, e_c, e_p, scale)
 
 
-@pytest.mark.parametrize("B,T", [(100, 6), (128, 3), (65, 4), (37, 3)])
-def test_hyper_cell_and_modulation_one_launch(B, T):
-    """csrc/hyper_mod.hip skr_hyper_cell_mod: wave 0 of modulation workgroup b
-    runs the hyper cell of row b (row kernel body, hh stored write-through),
-    every tile prefetches P / xh / R, waits for all rows and reads hh with sc1
-    loads -- against the two launches and the fp32 oracle (outputs, finals,
-    dz, every gradient; dropout on): error <= 1.5 x the two-launch error +
-    1e-3 of the largest element (the row body sums in another order than the
-    clustered hyper cell); NaN-poisoned hh rows before every launch (a tile
-    reading ahead of the rows) must not change a bit; it ran T times for
-    65 <= B <= 128 and not at all outside."""
-    from sketch_rnn_amd.ops import hyper
-    p, x, z, st, w = _hyper_setup(7, T, B, 5, 16, 2048, 256, 32, jitter=0.02, state=0.1)
-    runs, launched = {}, {}
-    saved = hyper.CELL_MOD, hyper.CELL_MOD_POISON
-    try:
-        for name, backend, dt, on, pois in (("ref", "torch", "fp32", False, False), ("cm", "hip", "bf16", True, False),
-                                            ("plain", "hip", "bf16", False, False), ("cm_p", "hip", "bf16", True, True)):
-            hyper.CELL_MOD, hyper.CELL_MOD_POISON = on, pois
-            ops.set_backend(backend)
-            ops.set_compute_dtype(dt)
-            n0 = hyper.CELL_MOD_STATS["launches"]
-            runs[name] = _hyper_run(p, x, z, st, w, keep=0.9, hkeep=0.9)
-            launched[name] = hyper.CELL_MOD_STATS["launches"] - n0
-    finally:
-        hyper.CELL_MOD, hyper.CELL_MOD_POISON = saved
-    want = T if 65 <= B <= 128 else 0
-    assert launched["cm"] == launched["cm_p"] == want and launched["plain"] == 0, launched
-    for i, n in enumerate(_names(p)):
-        assert torch.isfinite(runs["cm_p"][i]).all(), n
-        assert torch.equal(runs["cm"][i], runs["cm_p"][i]), n
-        ref = runs["ref"][i].float()
-        scale = max(ref.abs().max().item(), 1e-3)
-        e_c = (runs["cm"][i].float() - ref).abs().max().item()
-        e_p = (runs["plain"][i].float() - ref).abs().max().item()
-        assert e_c <= 1.5 * e_p + 1e-3 * scale, (n, e_c, e_p, scale)
-
-
-@pytest.mark.parametrize("B,T,fin_w", [(100, 7, True), (100, 5, False), (37, 4, True), (128, 3, False),
-                                       (192, 4, True), (256, 3, False)])
-def test_hyper_three_stage_chain_bitwise(B, T, fin_w):
-    """csrc/chain_step.hip skr_chain_bwd_main3: dvec P^T computed by the
-    producer workgroups of the chained launch (weight slice staged in LDS
-    while the rows compute, A operand through sc1 loads after the rows'
-    counter) equals the separate dvec P^T launch bit for bit -- the same
-    fragments, k order and MFMA -- for every output and gradient; and the
-    launch really ran T - 1 times (B <= 128).  At 4 dR_hyp W_y^T slabs: the
-    default cap of 2 leaves fewer producer tiles than dvec P^T tail tiles, so
-    the three-stage launch declines (-2) and the two-stage chain runs."""
-    from sketch_rnn_amd.ops import hyper
-    from sketch_rnn_amd.ops.recurrent import ROW_STATS
-    p, x, z, st, w = _hyper_setup(8, T, B, 5, 16, 2048, 256, 32, jitter=0.02, state=0.1)
-    ops.set_backend("hip")
-    ops.set_compute_dtype("bf16")
-    saved = hyper.CHAIN, hyper.CHAIN3, hyper.SAY_CAP
-    runs = {}
-    try:
-        hyper.CHAIN, hyper.SAY_CAP = True, 4
-        for c3 in (True, False, True):
-            hyper.CHAIN3 = c3
-            n0 = ROW_STATS["chain3"]
-            runs.setdefault(c3, []).append(_hyper_run(p, x, z, st, w, keep=0.9, hkeep=0.9, fin_w=fin_w))
-            # (B > 128: the tail is one 128-row block only -- not taken, two-stage chain)
-            assert ROW_STATS["chain3"] - n0 == ((T - 1) if (c3 and B <= 128) else 0)
-    finally:
-        hyper.CHAIN, hyper.CHAIN3, hyper.SAY_CAP = saved
-    for n, a, b, c in zip(_names(p), runs[True][0], runs[False][0], runs[True][1]):
-        assert torch.equal(a, c), n
-        assert torch.equal(a, b), n
-
-
 @pytest.mark.parametrize("B,T", [(100, 7), (37, 4), (128, 3), (192, 4)])
 def test_hyper_chained_rows_split_over_two_workgroups(B, T):
     """ops.hyper.CHAIN_CL = 2: each chained main-cell backward row on two
@@ -1384,26 +1313,38 @@ def test_hyper_chained_rows_split_over_two_workgroups(B, T):
         assert e_2 <= 1.5 * e_1 + 1e-3 * scale, (n, e_2, e_1, scale)
 
 
-@pytest.mark.parametrize("B,T", [(100, 7), (192, 4)])
-def test_hyper_chained_rows_never_overtake_the_counter(B, T):
+@pytest.mark.parametrize("B,T,say_cap", [pytest.param(100, 7, None, id="100-7"), pytest.param(192, 4, None, id="192-4"),
+                                         pytest.param(100, 5, 4, id="100-5-say_cap4")])
+def test_hyper_chained_rows_never_overtake_the_counter(B, T, say_cap):
     """Poison mode (ops.hyper.CHAIN_POISON): the d[h | hh] slabs are NaN-filled
     before every chained launch, so a main-cell row that read them before its
     producer tiles had written them would carry NaN into the gradients. Every
     output and gradient must be finite and equal to the unpoisoned chained run
-    bit for bit."""
+    bit for bit, with T - 1 chained launches in each run. say_cap: the
+    split-K ceiling ops.hyper.SAY_CAP (None: its default of 2) -- at 4 the
+    chained row reads four slabs, the only run of that count."""
     from sketch_rnn_amd.ops import hyper
+    from sketch_rnn_amd.ops.recurrent import ROW_STATS
     p, x, z, st, w = _hyper_setup(5, T, B, 5, 16, 2048, 256, 32, jitter=0.02, state=0.1)
     ops.set_backend("hip")
     ops.set_compute_dtype("bf16")
-    saved = hyper.CHAIN, hyper.CHAIN_POISON
+    saved = hyper.CHAIN, hyper.CHAIN_POISON, hyper.SAY_CAP
     try:
         hyper.CHAIN = True
+        if say_cap is not None:
+            # the ceiling binds: dR_hyp W_y^T ([B, 1024] x [1024, 2304]) is planned at no fewer splits, and
+            # 1024 / 64 K tiles divide by it, so _HyperSeq.backward runs exactly say_cap slabs
+            from sketch_rnn_amd.ops import gemm
+            assert gemm.plan_splits(B, 2048 + 256, 4 * 256, 1, torch.bfloat16) >= say_cap and (4 * 256 // 64) % say_cap == 0
+            hyper.SAY_CAP = say_cap
         hyper.CHAIN_POISON = False
+        n0 = ROW_STATS["chain"]
         clean = _hyper_run(p, x, z, st, w, keep=0.9, hkeep=0.9)
         hyper.CHAIN_POISON = True
         pois = _hyper_run(p, x, z, st, w, keep=0.9, hkeep=0.9)
+        assert ROW_STATS["chain"] - n0 == 2 * (T - 1)
     finally:
-        hyper.CHAIN, hyper.CHAIN_POISON = saved
+        hyper.CHAIN, hyper.CHAIN_POISON, hyper.SAY_CAP = saved
     for n, a, b in zip(_names(p), clean, pois):
         assert torch.isfinite(b).all(), n
         assert torch.equal(a, b), n
