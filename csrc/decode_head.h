@@ -71,6 +71,17 @@ __device__ void head_body(const Args& a, int rb, unsigned char* smem) {
         fin[k] = b < B && a.done[b] != 0;
         nf[k] = (b < B && a.nforced != nullptr) ? a.nforced[b] : 0;
     }
+    // Row temperatures, once per launch, in ONE register: lane k holds that of the wave's k-th sampled
+    // row, temps[b] (local row) or the launch's scalar; the draw reads it back with readlane. The scalar
+    // goes in as a value first: written as a select between the two loads, the compiler selects between
+    // their addresses, gives the kernel argument a scratch slot and the launch scratch memory.
+    float tp = a.temp;
+    asm volatile("" : "+v"(tp));
+    {
+        const int b = rb * RB + w + 8 * lane;
+        if (lane < RPW && b < B && a.temps != nullptr) tp = a.temps[b];
+    }
+    const float itp = 1.f / tp;         // the reciprocal too: one division per launch, none per stroke
     bool ok = true;
 
     for (int t = a.t0; t < a.t1; ++t) {
@@ -100,7 +111,9 @@ __device__ void head_body(const Args& a, int rb, unsigned char* smem) {
             const int r = w + 8 * k, b = rb * RB + r;
             if (b >= B) continue;   // wave-uniform
             const float* zr = zs + r * ldz;
-            const MdnDraw dr = mdn_sample_wave(zr, M, 1, a.temp, a.greedy, 0, key, (uint32_t)(a.row0 + b), (uint32_t)t);
+            const float tk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tp), k));
+            const float itk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(itp), k));
+            const MdnDraw dr = mdn_sample_wave(zr, M, 1, tk, itk, a.greedy, 0, key, (uint32_t)(a.row0 + b), (uint32_t)t);
             const uint32_t xoff = (uint32_t)((((int64_t)(t + 1) * B + b) * kXLd) * 4);
             if (t < nf[k]) {          // prefix: the host's x(t+1) stands (wave-uniform)
 #pragma unroll

@@ -52,6 +52,7 @@ struct DecArgs {
     float* xin;                          // [N+1][B][8] fed inputs (x(0) from the host; forced: all from the host)
     float* out;                          // [B][N][5] strokes (finished rows: end-of-sketch padding)
     int* done;                           // [B], zeroed by the host
+    const float* temps;                  // [B] per-row temperature in place of temp, or null
     float* zout;                         // [N][B][nout] head outputs, or null
     const int64_t* seed;
     uint32_t* flags;                     // [nrb][kFlagStride] epochs (zeroed per launch)
@@ -274,6 +275,14 @@ __device__ void head_body(const DecArgs& a, int rb, unsigned char* smem) {
     bool fin[RPW];                      // row finished (eoc drawn): emits padding from the next step
 #pragma unroll
     for (int k = 0; k < RPW; ++k) fin[k] = false;
+    // row temperatures in one register: lane k holds that of the wave's k-th sampled row (decode_head.h)
+    float tp = a.temp;
+    asm volatile("" : "+v"(tp));
+    {
+        const int b = rb * RB + w + 8 * lane;
+        if (lane < RPW && b < B && a.temps != nullptr) tp = a.temps[b];
+    }
+    const float itp = 1.f / tp;
     bool ok = true;
 
     for (int t = 0; t < N; ++t) {
@@ -303,7 +312,9 @@ __device__ void head_body(const DecArgs& a, int rb, unsigned char* smem) {
             const int r = w + 8 * k, b = rb * RB + r;
             if (b >= B) continue;   // wave-uniform
             const float* zr = zs + r * ldz;
-            dr[k] = mdn_sample_wave(zr, M, a.mode, a.temp, a.greedy, a.fix_pen, key, (uint32_t)(a.row0 + b),
+            const float tk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tp), k));
+            const float itk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(itp), k));
+            dr[k] = mdn_sample_wave(zr, M, a.mode, tk, itk, a.greedy, a.fix_pen, key, (uint32_t)(a.row0 + b),
                                     (uint32_t)t);
             if (!a.forced && lane < 5) {
                 const float v = lane == 0 ? dr[k].row[0] : lane == 1 ? dr[k].row[1] : lane == 2 ? dr[k].row[2]

@@ -38,6 +38,7 @@ struct DecodeSample {
     int* done;                         // [B] eos reached
     const float* forced; int64_t ld_forced;   // rows with step < nforced[b] emit forced[b] instead of
     const int* nforced;                // their draw (mdn_sample.h; nullptr: none)
+    const float* temps;                // [B] per-row temperature in place of temp (nullptr: temp)
 };
 
 namespace {
@@ -73,14 +74,16 @@ __global__ __launch_bounds__(256) void decode_hyper_cell(const FwdArgs a, const 
     }
     const float lcg = a.lnc_g[u], lcb = a.lnc_b[u];
     const float cp = a.c_prev[(int64_t)b * H + u];
-    const float fv = skr::mdn_forced_load(s.forced, s.ld_forced, s.active ? s.nforced : nullptr, b);
+    const float* temps = s.active ? s.temps : nullptr;
+    const float fv = skr::mdn_forced_load(s.forced, s.ld_forced, s.active ? s.nforced : nullptr, temps, b);
     // ---- stroke t-1: fold + draw (or the given x)
     if (s.active) {
         skr::fold_head_slabs(s.zs, s.ldz, s.nslab, s.slab, s.bias, s.nout, b, part, zrow);
         if (w == 0) {
             const uint32_t key = skr::hash_key(*s.seed, 0x5A3Du, s.step);
+            const float tb = skr::mdn_temp_gather(fv, temps, s.temp);
             const skr::MdnDraw d =
-                skr::mdn_sample_wave(zrow, s.M, s.mode, s.temp, s.greedy, s.fix_pen, key, (uint32_t)(s.row0 + b), s.step);
+                skr::mdn_sample_wave(zrow, s.M, s.mode, tb, 1.f / tb, s.greedy, s.fix_pen, key, (uint32_t)(s.row0 + b), s.step);
             const skr::MdnForced fz = skr::mdn_forced_gather(fv);
             if (lane == 0) skr::mdn_emit_row(d, fz, s.step, s.mode, s.out_row + b * s.ld_out, x + b * 5, s.done + b, xr);
         }

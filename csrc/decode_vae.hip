@@ -58,6 +58,7 @@ struct DecVaeArgs {
     float* out;                          // [B][N][5] strokes
     int* done;                           // [B] finished state: read at t0, written after t1 - 1
     const int* nforced;                  // [B] leading strokes taken from xin, or null (0)
+    const float* temps;                  // [B] per-row temperature in place of temp, or null
     float* zout;                         // [N][B][nout] head outputs, or null
     const int64_t* seed;
     uint32_t* flags;                     // [nrb][kFlagStride] epochs (zeroed per launch)

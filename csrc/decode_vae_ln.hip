@@ -67,6 +67,7 @@ struct DecVaeLnArgs {
     float* out;                          // [B][N][5] strokes
     int* done;                           // [B] finished state: read at t0, written after t1 - 1
     const int* nforced;                  // [B] leading strokes taken from xin, or null (0)
+    const float* temps;                  // [B] per-row temperature in place of temp, or null
     float* zout;                         // [N][B][nout] head outputs, or null
     float* gstat;                        // [2][nrb][H/16][16*mtw][4][2] gate (mean, M2) partials
     float* cstat;                        // [2][nrb][H/16][16*mtw][2] cell (mean, M2) partials

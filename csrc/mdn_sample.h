@@ -29,12 +29,13 @@ struct MdnDraw {
 // Every lane of the wave must be active; the result is wave-uniform. The pi
 // softmax runs across lanes (lane k holds component k); the inverse CDF then
 // sums the M probabilities in component order with scalar adds (readlane),
-// the same fp32 order as a sequential loop.
-__device__ inline MdnDraw mdn_sample_wave(const float* zr, int M, int mode, float temp, int greedy, int fix_pen,
-                                          uint32_t key, uint32_t b, uint32_t step) {
+// the same fp32 order as a sequential loop. inv_temp = 1.f / temp, formed by
+// the caller: a kernel that draws many strokes of a row divides once.
+__device__ inline MdnDraw mdn_sample_wave(const float* zr, int M, int mode, float temp, float inv_temp, int greedy,
+                                          int fix_pen, uint32_t key, uint32_t b, uint32_t step) {
     const int lane = threadIdx.x & 63;
     const bool use_t = mode == 1 || step > 1;
-    const float inv_t = use_t ? 1.f / temp : 1.f;
+    const float inv_t = use_t ? inv_temp : 1.f;
     const bool on = lane < M;
     const float l = on ? zr[3 + lane] * inv_t : -INFINITY;
     float m = l;
@@ -64,7 +65,7 @@ __device__ inline MdnDraw mdn_sample_wave(const float* zr, int M, int mode, floa
         }
     }
     // pen
-    const float pt = (mode == 1 || (fix_pen && step > 1)) ? 1.f / temp : 1.f;
+    const float pt = (mode == 1 || (fix_pen && step > 1)) ? inv_temp : 1.f;
     float pl[3] = {zr[0] * pt, zr[1] * pt, zr[2] * pt};
     const float pm = fmaxf(pl[0], fmaxf(pl[1], pl[2]));
     float pp[3], ps = 0.f;
@@ -122,23 +123,35 @@ struct MdnForced {
     __device__ bool on(uint32_t step) const { return (int64_t)step < (int64_t)n; }
 };
 
-// The loads of row b's forced stroke, held across wave 0: lane k < 5 gets
-// forced[b][k], lane 5 the bits of nforced[b] (0 when nforced is null). Callers
-// issue it with their other early loads, before the slab fold and the draw.
-// Per-lane vector loads whose only condition is the kernel argument `nforced`:
-// nothing waits for them until mdn_forced_gather -- a wave-uniform scalar
-// load of nforced[b] would be awaited on the spot, one memory latency in front
-// of the fold. forced[b] must be readable for every row whenever nforced is
-// given, forced row or not.
+// The loads of row b's forced stroke and temperature, held across wave 0: lane
+// k < 5 gets forced[b][k], lane 5 the bits of nforced[b] (0 when nforced is
+// null), lane 6 temps[b] (when temps is given). Callers issue it with their
+// other early loads, before the slab fold and the draw. One per-lane vector
+// load whose only conditions are the kernel arguments `nforced` and `temps`:
+// nothing waits for it until mdn_temp_gather / mdn_forced_gather -- a
+// wave-uniform scalar load of nforced[b] or temps[b] would be awaited on the
+// spot, one memory latency in front of the fold. forced[b] must be readable
+// for every row whenever nforced is given, forced row or not.
 __device__ inline float mdn_forced_load(const float* __restrict__ forced, int64_t ld_forced,
-                                        const int* __restrict__ nforced, int b) {
+                                        const int* __restrict__ nforced, const float* __restrict__ temps, int b) {
     const int lane = threadIdx.x;           // wave 0 samples in every kernel: the other waves load nothing
     float v = 0.f;
-    if (nforced != nullptr && lane < 6) {   // one load, its address chosen per lane (so it stays a vector load)
+    // one load, its address chosen per lane (so it stays a vector load); the three addresses are formed
+    // outside the selects, so these stay selects (inside them the compiler branches around the products)
+    const bool mine = ((lane < 6) & (nforced != nullptr)) | ((lane == 6) & (temps != nullptr));   // no branches
+    if (mine) {
         const float* fr = forced + (int64_t)b * ld_forced + lane;
-        v = *(lane < 5 ? fr : reinterpret_cast<const float*>(nforced + b));
+        const float* sc = lane == 5 ? reinterpret_cast<const float*>(nforced + b) : temps + b;
+        v = *(lane < 5 ? fr : sc);
     }
     return v;
+}
+
+// Row b's sampling temperature: temps[b] out of mdn_forced_load's value (local
+// row, like done and nforced), or the launch's scalar when temps is null.
+// Every lane of the wave must be active; the result is wave-uniform.
+__device__ inline float mdn_temp_gather(float v, const float* temps, float temp) {
+    return temps != nullptr ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 6)) : temp;
 }
 
 // Every lane of the wave must be active; the result is wave-uniform.

@@ -18,6 +18,10 @@
 // Sketch completion: the *_forced entry points take per-row given strokes;
 // a row with step < nforced[b] emits forced[b] instead of its draw
 // (mdn_sample.h: MdnForced, mdn_emit_row).
+//
+// Per-row temperature: the *_temps entry points take temps [B] (indexed by the
+// launch's local row, like done and nforced); row b then uses temps[b] where
+// the others use the scalar temp (mdn_sample.h: mdn_temp_gather).
 #include "mdn_sample.h"
 
 namespace {
@@ -28,11 +32,13 @@ __global__ __launch_bounds__(64) void mdn_sample_kernel(const float* __restrict_
                                                         float* __restrict__ next_x, int64_t ld_next,
                                                         int* __restrict__ done, float* __restrict__ params,
                                                         const float* __restrict__ forced, int64_t ld_forced,
-                                                        const int* __restrict__ nforced) {
+                                                        const int* __restrict__ nforced,
+                                                        const float* __restrict__ temps) {
     const int b = blockIdx.x, lane = threadIdx.x;
-    const float fv = skr::mdn_forced_load(forced, ld_forced, nforced, b);
+    const float fv = skr::mdn_forced_load(forced, ld_forced, nforced, temps, b);
     const uint32_t key = skr::hash_key(*seed, 0x5A3Du, step);
-    const skr::MdnDraw d = skr::mdn_sample_wave(z + b * ldz, M, mode, temp, greedy, fix_pen, key, (uint32_t)b, step);
+    const float tb = skr::mdn_temp_gather(fv, temps, temp);
+    const skr::MdnDraw d = skr::mdn_sample_wave(z + b * ldz, M, mode, tb, 1.f / tb, greedy, fix_pen, key, (uint32_t)b, step);
     const skr::MdnForced f = skr::mdn_forced_gather(fv);
     if (lane != 0) return;
     skr::mdn_emit_row(d, f, step, mode, out_row + b * ld_out, next_x + b * ld_next, done + b);
@@ -58,15 +64,17 @@ __global__ __launch_bounds__(256) void mdn_sample_slabs_kernel(const float* __re
                                                                float* __restrict__ next_x, int64_t ld_next,
                                                                int* __restrict__ done,
                                                                const float* __restrict__ forced, int64_t ld_forced,
-                                                               const int* __restrict__ nforced) {
+                                                               const int* __restrict__ nforced,
+                                                               const float* __restrict__ temps) {
     __shared__ float part[4][256];
     __shared__ float zrow[256];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const float fv = skr::mdn_forced_load(forced, ld_forced, nforced, b);
+    const float fv = skr::mdn_forced_load(forced, ld_forced, nforced, temps, b);
     skr::fold_head_slabs(zs, ldz, nslab, slab, bias, nout, b, part, zrow);
     if (w != 0) return;
     const uint32_t key = skr::hash_key(*seed, 0x5A3Du, step);
-    const skr::MdnDraw d = skr::mdn_sample_wave(zrow, M, mode, temp, greedy, fix_pen, key, (uint32_t)(row0 + b), step);
+    const float tb = skr::mdn_temp_gather(fv, temps, temp);
+    const skr::MdnDraw d = skr::mdn_sample_wave(zrow, M, mode, tb, 1.f / tb, greedy, fix_pen, key, (uint32_t)(row0 + b), step);
     const skr::MdnForced f = skr::mdn_forced_gather(fv);
     if (lane != 0) return;
     skr::mdn_emit_row(d, f, step, mode, out_row + b * ld_out, next_x + b * ld_next, done + b);
@@ -76,19 +84,29 @@ __global__ __launch_bounds__(256) void mdn_sample_slabs_kernel(const float* __re
 
 // forced [B][ld_forced] / nforced [B] (indexed like `done`, by local row): rows
 // with step < nforced[b] emit forced[b] instead of their draw (mdn_sample.h;
-// every row of forced is read when nforced is given).
-SKR_API int skr_mdn_sample_slabs_forced(const float* zs, int64_t ldz, int nslab, int64_t slab, const float* bias, int B,
-                                        int M, int mode, float temp, int greedy, int fix_pen, const int64_t* seed,
-                                        uint32_t step, int row0, float* out_row, int64_t ld_out, float* next_x,
-                                        int64_t ld_next, int* done, const float* forced, int64_t ld_forced,
-                                        const int* nforced, hipStream_t s) {
+// every row of forced is read when nforced is given). temps [B] (local rows
+// too): row b's temperature in place of temp; nullptr: temp for every row.
+SKR_API int skr_mdn_sample_slabs_temps(const float* zs, int64_t ldz, int nslab, int64_t slab, const float* bias, int B,
+                                       int M, int mode, float temp, int greedy, int fix_pen, const int64_t* seed,
+                                       uint32_t step, int row0, float* out_row, int64_t ld_out, float* next_x,
+                                       int64_t ld_next, int* done, const float* forced, int64_t ld_forced,
+                                       const int* nforced, const float* temps, hipStream_t s) {
     if (M < 1 || M > 32 || nslab < 1) return -2;
     if (nforced != nullptr && forced == nullptr) return -2;
     if (B <= 0) return 0;
     hipLaunchKernelGGL(mdn_sample_slabs_kernel, dim3(B), dim3(256), 0, s, zs, ldz, nslab, slab, bias, 3 + 6 * M, M,
                        mode, temp, greedy, fix_pen, seed, step, row0, out_row, ld_out, next_x, ld_next, done, forced,
-                       ld_forced, nforced);
+                       ld_forced, nforced, temps);
     return SKR_CHECK_LAUNCH();
+}
+
+SKR_API int skr_mdn_sample_slabs_forced(const float* zs, int64_t ldz, int nslab, int64_t slab, const float* bias, int B,
+                                        int M, int mode, float temp, int greedy, int fix_pen, const int64_t* seed,
+                                        uint32_t step, int row0, float* out_row, int64_t ld_out, float* next_x,
+                                        int64_t ld_next, int* done, const float* forced, int64_t ld_forced,
+                                        const int* nforced, hipStream_t s) {
+    return skr_mdn_sample_slabs_temps(zs, ldz, nslab, slab, bias, B, M, mode, temp, greedy, fix_pen, seed, step, row0,
+                                      out_row, ld_out, next_x, ld_next, done, forced, ld_forced, nforced, nullptr, s);
 }
 
 SKR_API int skr_mdn_sample_slabs(const float* zs, int64_t ldz, int nslab, int64_t slab, const float* bias, int B,
@@ -99,16 +117,24 @@ SKR_API int skr_mdn_sample_slabs(const float* zs, int64_t ldz, int nslab, int64_
                                        out_row, ld_out, next_x, ld_next, done, nullptr, 0, nullptr, s);
 }
 
-SKR_API int skr_mdn_sample_forced(const float* z, int64_t ldz, int B, int M, int mode, float temp, int greedy,
-                                  int fix_pen, const int64_t* seed, uint32_t step, float* out_row, int64_t ld_out,
-                                  float* next_x, int64_t ld_next, int* done, float* params, const float* forced,
-                                  int64_t ld_forced, const int* nforced, hipStream_t s) {
+SKR_API int skr_mdn_sample_temps(const float* z, int64_t ldz, int B, int M, int mode, float temp, int greedy,
+                                 int fix_pen, const int64_t* seed, uint32_t step, float* out_row, int64_t ld_out,
+                                 float* next_x, int64_t ld_next, int* done, float* params, const float* forced,
+                                 int64_t ld_forced, const int* nforced, const float* temps, hipStream_t s) {
     if (M < 1 || M > 32) return -2;
     if (nforced != nullptr && forced == nullptr) return -2;
     if (B <= 0) return 0;
     hipLaunchKernelGGL(mdn_sample_kernel, dim3(B), dim3(64), 0, s, z, ldz, M, mode, temp, greedy, fix_pen, seed, step,
-                       out_row, ld_out, next_x, ld_next, done, params, forced, ld_forced, nforced);
+                       out_row, ld_out, next_x, ld_next, done, params, forced, ld_forced, nforced, temps);
     return SKR_CHECK_LAUNCH();
+}
+
+SKR_API int skr_mdn_sample_forced(const float* z, int64_t ldz, int B, int M, int mode, float temp, int greedy,
+                                  int fix_pen, const int64_t* seed, uint32_t step, float* out_row, int64_t ld_out,
+                                  float* next_x, int64_t ld_next, int* done, float* params, const float* forced,
+                                  int64_t ld_forced, const int* nforced, hipStream_t s) {
+    return skr_mdn_sample_temps(z, ldz, B, M, mode, temp, greedy, fix_pen, seed, step, out_row, ld_out, next_x, ld_next,
+                                done, params, forced, ld_forced, nforced, nullptr, s);
 }
 
 SKR_API int skr_mdn_sample(const float* z, int64_t ldz, int B, int M, int mode, float temp, int greedy, int fix_pen,

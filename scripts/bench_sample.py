@@ -25,6 +25,10 @@ makes every throughput look like padding).
 ``--prefix_len P`` (sketch completion, both ``--impl`` arms) feeds a synthetic
 P-stroke pen-down prefix to every row; the decoder continues from it.
 
+``--temperatures T0,T1,...`` (both ``--impl`` arms) decodes with a
+temperature per row, the listed values spread over the rows in turn
+(``run(temperature=)``); the decoder is still built at ``--temperature``.
+
 usage: python scripts/bench_sample.py [--config vae_large] [--batch 256] [--steps 250] [--train-steps 0]
 """
 from __future__ import annotations
@@ -55,6 +59,8 @@ def main():
                          "layer_norm decoders)")
     ap.add_argument("--prefix_len", type=int, default=0,
                     help="feed a synthetic prefix of this many strokes to every row (sketch completion)")
+    ap.add_argument("--temperatures", default=None,
+                    help="comma-separated temperatures spread over the rows in turn (per-row temperature)")
     a = ap.parse_args()
     if not 0 <= a.prefix_len <= a.steps:
         ap.error("--prefix_len must lie in [0, --steps]")
@@ -92,6 +98,9 @@ def main():
                                   generator=torch.Generator(device="cuda").manual_seed(0)) * 0.5
         p5[..., 2] = 1.0
         pre = dict(prefix=p5)
+    if a.temperatures is not None:
+        tv = torch.tensor([float(t) for t in a.temperatures.split(",")], device="cuda")
+        pre["temperature"] = tv[torch.arange(a.batch, device="cuda") % tv.numel()]
     dec, impl = None, a.impl
     if a.impl == "fused":
         from sketch_rnn_amd.sample.fused import NotCoResident, fused_vae_decoder
@@ -124,6 +133,7 @@ def main():
     print(json.dumps({"metric": "sampled valid strokes/sec (temperature %.2f)" % a.temperature, "config": a.config,
                       "impl": impl, "dtype": a.dtype, "fp8_gemm": bool(a.fp8), "batch": a.batch, "steps": a.steps, "train_steps": a.train_steps,
                       "train_cost": train_cost, "early_exit": not a.no_early_exit, "prefix_len": a.prefix_len,
+                      "temperatures": a.temperatures,
                       "valid_strokes_per_s": round(valid_sps, 1),
                       "decode_positions_per_s": round(total_pos / wall, 1),
                       "steps_run": total_pos / a.batch / a.reps,

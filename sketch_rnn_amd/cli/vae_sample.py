@@ -17,6 +17,12 @@ sketches from a dataset (``--data`` / ``--synthetic`` / ``--split`` as in
   sketch, or the ``prior``. The grid holds each prefix followed by its K
   completions.
 
+``--temperatures 0.1,0.4,0.7,1.0`` (modes ``random``, ``class`` and
+``reconstruct``) decodes each of the ``--n`` latents once per listed
+temperature, all in one batch with a temperature per row, and lays the grid
+out with one line per latent and the temperatures as its columns (after the
+original in ``reconstruct``).
+
 Writes a stroke-3 SVG grid.
 ``--device_sampler`` decodes the whole grid in parallel through the
 HIP-graph decoder; with ``--fused`` a plain ``lstm`` or ``layer_norm``
@@ -53,6 +59,9 @@ def main(argv=None) -> int:
     p.add_argument("--n", type=int, default=10)
     p.add_argument("--label", type=int, default=0)
     p.add_argument("--temperature", type=float, default=0.5)
+    p.add_argument("--temperatures", default=None,
+                   help="random / class / reconstruct: comma-separated temperatures; every latent is decoded once "
+                        "per value in one batch, one grid line per latent (replaces --temperature)")
     p.add_argument("--greedy", action="store_true")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--device", default=None)
@@ -83,6 +92,16 @@ def main(argv=None) -> int:
     if a.fused and not a.device_sampler:
         p.error("--fused needs --device_sampler")
     from_data = a.mode in ("reconstruct", "complete")
+    temps = None
+    if a.temperatures is not None:
+        if a.mode not in ("random", "class", "reconstruct"):
+            p.error("--temperatures works in the modes random, class and reconstruct")
+        try:
+            temps = [float(t) for t in a.temperatures.split(",")]
+        except ValueError:
+            p.error("--temperatures must be comma-separated numbers")
+        if not all(math.isfinite(t) and t > 0 for t in temps):
+            p.error("--temperatures must be finite and greater than 0")
     if a.mode == "complete" and (a.completions < 1 or not 0.0 <= a.prefix_frac <= 1.0):
         p.error("--completions must be >= 1 and --prefix_frac in [0, 1]")
     import torch
@@ -149,15 +168,22 @@ def main(argv=None) -> int:
                 zs = rng.randn(a.n * group, cfg.z_size)
             labels = np.repeat(labels, group)
             prefix, plen = np.repeat(pre, group, axis=0), np.repeat(np.asarray(k, np.int64), group)
+    row_temps = None                  # --temperatures: row i * K + j decodes latent i at temperature j
+    if temps is not None:
+        group = len(temps)
+        zs, labels = np.repeat(zs, group, axis=0), np.repeat(labels, group)
+        row_temps = np.tile(np.asarray(temps, np.float64), a.n)
     rows = len(labels)
     sketches = []
     if a.fused and not device.startswith("cuda"):
         print("--fused: no GPU device, sampling on the host")
-    if a.device_sampler and (device.startswith("cuda") or from_data):
+    if a.device_sampler and (device.startswith("cuda") or from_data or temps is not None):
         zt, lt = torch.as_tensor(zs, dtype=torch.float32, device=device), torch.as_tensor(labels, device=device)
         pre_kw = {}
         if prefix is not None:
             pre_kw = dict(prefix=torch.as_tensor(prefix, device=device), prefix_len=torch.as_tensor(plen, device=device))
+        if row_temps is not None:
+            pre_kw.update(temperature=torch.as_tensor(row_temps, device=device))
         s = None
         if not device.startswith("cuda"):
             a.fused = False
@@ -179,12 +205,16 @@ def main(argv=None) -> int:
         for k in range(rows):
             z = torch.as_tensor(zs[k:k + 1], dtype=torch.float32, device=device)
             pre_k = None if prefix is None else prefix[k, :plen[k]]
-            s5, _ = sample_vae(model, cfg.max_seq_len, a.temperature, a.greedy, z=z, label=int(labels[k]), rng=rng,
+            temp_k = a.temperature if row_temps is None else float(row_temps[k])
+            s5, _ = sample_vae(model, cfg.max_seq_len, temp_k, a.greedy, z=z, label=int(labels[k]), rng=rng,
                                prefix=pre_k)
             sketches.append(to_normal_strokes(s5))
     if shown is not None:       # each data sketch (or its prefix) followed by what was decoded from it
         sketches = [x for i, d in enumerate(shown) for x in [d] + sketches[i * group:(i + 1) * group]]
-    grid_strokes3(sketches, a.out)
+    if temps is not None:       # one line per latent
+        grid_strokes3(sketches, a.out, maxcol=len(sketches) // a.n)
+    else:
+        grid_strokes3(sketches, a.out)
     print("wrote %s (%d sketches)" % (a.out, len(sketches)))
     return 0
 

@@ -262,7 +262,7 @@ class DecArgs(C.Structure):
         ("temp", _f), ("forget_bias", _f),
         ("ly", DecLayer * 2),
         ("Wx0", _p), ("WoT", _p), ("bo", _p),
-        ("xin", _p), ("out", _p), ("done", _p), ("zout", _p),
+        ("xin", _p), ("out", _p), ("done", _p), ("temps", _p), ("zout", _p),
         ("seed", _p), ("flags", _p), ("err", _p),
     ]
 
@@ -275,7 +275,7 @@ class DecVaeArgs(C.Structure):
         ("temp", _f), ("forget_bias", _f),
         ("WT", _p), ("Wx", _p), ("zb", _p), ("c0", _p), ("cT", _p), ("hbuf", _p),
         ("WoT", _p), ("bo", _p),
-        ("xin", _p), ("out", _p), ("done", _p), ("nforced", _p), ("zout", _p),
+        ("xin", _p), ("out", _p), ("done", _p), ("nforced", _p), ("temps", _p), ("zout", _p),
         ("seed", _p), ("flags", _p), ("err", _p),
     ]
 
@@ -289,7 +289,7 @@ class DecVaeLnArgs(C.Structure):
         ("WT", _p), ("Wx", _p), ("zp", _p), ("ln_g", _p), ("ln_b", _p), ("lnc_g", _p), ("lnc_b", _p),
         ("c0", _p), ("cT", _p), ("hbuf", _p),
         ("WoT", _p), ("bo", _p),
-        ("xin", _p), ("out", _p), ("done", _p), ("nforced", _p), ("zout", _p),
+        ("xin", _p), ("out", _p), ("done", _p), ("nforced", _p), ("temps", _p), ("zout", _p),
         ("gstat", _p), ("cstat", _p),
         ("seed", _p), ("flags", _p), ("err", _p),
     ]
@@ -353,6 +353,7 @@ class DecodeSample(C.Structure):
         ("out_row", _p), ("ld_out", _i64),
         ("done", _p),
         ("forced", _p), ("ld_forced", _i64), ("nforced", _p),
+        ("temps", _p),
     ]
 
 
@@ -402,6 +403,12 @@ class HipLib:
         lib.skr_mdn_sample_slabs_forced.argtypes = [_p, _i64, _i, _i64, _p, _i, _i, _i, _f, _i, _i, _p, _u32, _i, _p,
                                                     _i64, _p, _i64, _p, _p, _i64, _p, _p]
         lib.skr_mdn_sample_slabs_forced.restype = _i
+        lib.skr_mdn_sample_temps.argtypes = [_p, _i64, _i, _i, _i, _f, _i, _i, _p, _u32, _p, _i64, _p, _i64, _p, _p,
+                                             _p, _i64, _p, _p, _p]
+        lib.skr_mdn_sample_temps.restype = _i
+        lib.skr_mdn_sample_slabs_temps.argtypes = [_p, _i64, _i, _i64, _p, _i, _i, _i, _f, _i, _i, _p, _u32, _i, _p,
+                                                   _i64, _p, _i64, _p, _p, _i64, _p, _p, _p]
+        lib.skr_mdn_sample_slabs_temps.restype = _i
         lib.skr_inproj_fwd.argtypes = [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]
         lib.skr_inproj_fwd.restype = _i
         lib.skr_inproj_bwd.argtypes = [_p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p]

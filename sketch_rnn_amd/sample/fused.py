@@ -153,7 +153,8 @@ class FusedRefDecoder:
         self._w, self._sig = w, sig
         return w
 
-    def _launch(self, r0: int, Bc: int, xin: torch.Tensor, forced: bool, zout: Optional[torch.Tensor]):
+    def _launch(self, r0: int, Bc: int, xin: torch.Tensor, forced: bool, zout: Optional[torch.Tensor],
+                temps: Optional[torch.Tensor] = None):
         from ..ops._hipapi import DecArgs
         from ..ops.recurrent import cluster_error_flag
         w = self._weights()
@@ -183,6 +184,7 @@ class FusedRefDecoder:
         a.Wx0, a.WoT, a.bo = w["Wx0"].data_ptr(), w["WoT"].data_ptr(), w["bo"].data_ptr()
         a.xin, a.out, a.done = xin.data_ptr(), out.data_ptr(), done.data_ptr()
         a.zout = zout.data_ptr() if zout is not None else None
+        a.temps = temps[r0:].data_ptr() if temps is not None else None    # indexed by the launch's local row
         a.seed, a.flags, a.err = self.seed.data_ptr(), flags.data_ptr(), cluster_error_flag(dev).data_ptr()
         rc = self.lib.lib.skr_decode_ref(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         if rc == -8:
@@ -193,20 +195,24 @@ class FusedRefDecoder:
         return out, keep
 
     @torch.no_grad()
-    def run(self, seed: int = 0, return_z: bool = False):
+    def run(self, seed: int = 0, return_z: bool = False, temperature=None):
         """Returns ``(strokes, lengths)`` (plus the head outputs ``z [N, B, 3+6M]``
-        with ``return_z``)."""
+        with ``return_z``). ``temperature``: a float or a vector of B per-row
+        values for this run (None: the constructor's)."""
         from ..ops.recurrent import check_cluster_errors
+        from .sampler import check_temperature
+        temps = (torch.full((self.B,), self.temp, dtype=torch.float32, device=self.dev) if temperature is None
+                 else check_temperature("FusedRefDecoder.run", temperature, self.B, self.dev))
         self.seed.fill_(int(seed))
         outs, zs, keep = [], [], []
         for r0 in range(0, self.B, self.rows):
             Bc = min(self.rows, self.B - r0)
             xin = torch.zeros(self.N + 1, Bc, _XLD, device=self.dev)        # x(0) = 0 (model.py:200)
             zout = torch.empty(self.N, Bc, self.nout, device=self.dev) if return_z else None
-            o, k = self._launch(r0, Bc, xin, False, zout)
+            o, k = self._launch(r0, Bc, xin, False, zout, temps)
             outs.append(o)
             zs.append(zout)
-            keep += k + [xin]
+            keep += k + [xin, temps]
         strokes = torch.cat(outs, 0)
         check_cluster_errors(self.dev)
         hits = strokes[:, :, 3] > 0
@@ -315,7 +321,8 @@ class _FusedVAEBase:
         zc = self.model.condition(z if cfg.conditional else None, lab, B, dev)
         return zc, self.model.initial_state(zc, B, dev)
 
-    def _begin(self, seed: int, z, labels, xin: torch.Tensor, nforced: Optional[torch.Tensor], want_z: bool):
+    def _begin(self, seed: int, z, labels, xin: torch.Tensor, nforced: Optional[torch.Tensor], want_z: bool,
+               temps: Optional[torch.Tensor] = None):
         """Buffers of one decode: whole-batch ones the launches index by row
         slice, and per-launch-chunk ones laid out ``[step][row of the chunk]``."""
         w = self._weights()
@@ -326,6 +333,7 @@ class _FusedVAEBase:
             "out": torch.empty(B, N, 5, dtype=f32, device=dev),
             "done": torch.zeros(B, dtype=torch.int32, device=dev),
             "nforced": nforced.to(dev, torch.int32).contiguous() if nforced is not None else None,
+            "temps": temps,
             "chunks": [],
         }
         h0 = h0.to(torch.bfloat16)
@@ -375,6 +383,7 @@ class _FusedVAEBase:
         a.hbuf, a.xin = ch["hbuf"].data_ptr(), ch["xin"].data_ptr()
         a.out, a.done = st["out"][r0:].data_ptr(), st["done"][r0:].data_ptr()
         a.nforced = st["nforced"][r0:].data_ptr() if st["nforced"] is not None else None
+        a.temps = st["temps"][r0:].data_ptr() if st["temps"] is not None else None
         a.zout = ch["zout"].data_ptr() if ch["zout"] is not None else None
         a.seed, a.flags = self.seed.data_ptr(), ch["flags"].data_ptr()
         a.err = cluster_error_flag(self.dev).data_ptr()
@@ -393,16 +402,22 @@ class _FusedVAEBase:
     @torch.no_grad()
     def run(self, seed: int = 0, z: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
             prefix: Optional[torch.Tensor] = None, prefix_len: Optional[torch.Tensor] = None,
-            return_z: bool = False):
+            return_z: bool = False, temperature=None):
         """Returns ``(strokes [B, N, 5], lengths [B])`` like
         :meth:`GraphDecoder.run` (plus the head outputs ``z [N, B, 3+6M]`` with
         ``return_z``; steps an early exit skipped are zero there).
 
         ``prefix [B, P, 5]`` with ``prefix_len [B]`` (default P for every row)
         completes sketches: the first ``prefix_len[b]`` strokes of row b are
-        the prefix's and the decoder continues from them."""
+        the prefix's and the decoder continues from them.
+
+        ``temperature``: a float or a vector of B per-row values for this run
+        (None: the constructor's); each launch reads its rows' slice."""
         from ..ops.recurrent import check_cluster_errors
+        from .sampler import check_temperature
         B, N, dev = self.B, self.N, self.dev
+        temps = (torch.full((B,), self.temp, dtype=torch.float32, device=dev) if temperature is None
+                 else check_temperature(self._name + ".run", temperature, B, dev))
         self.seed.fill_(int(seed))
         xin = torch.zeros(N + 1, B, _XLD, device=dev)
         xin[0, :, 2] = 1.0                                          # start token
@@ -420,7 +435,7 @@ class _FusedVAEBase:
             if nforced is not None:
                 free = torch.arange(1, N + 1, device=dev)[:, None] > nforced[None, :]
             xin[1:][free] = float("nan")
-        st = self._begin(seed, z, labels, xin, nforced, return_z)
+        st = self._begin(seed, z, labels, xin, nforced, return_z, temps)
         ran = N
         for t0, t1 in self.ranges:
             for ch in st["chunks"]:

@@ -314,12 +314,14 @@ class HyperStepDecoder:
     # -- four-launch stroke -------------------------------------------------------
     def sample_args(self, step: int, row0: int, out_row: torch.Tensor, done: torch.Tensor, seed: torch.Tensor,
                     M: int, mode: int, temp: float, greedy: bool, fix_pen: bool,
-                    forced: torch.Tensor = None, nforced: torch.Tensor = None) -> DecodeSample:
+                    forced: torch.Tensor = None, nforced: torch.Tensor = None,
+                    temps: torch.Tensor = None) -> DecodeSample:
         """Sampler of stroke ``step`` (written to ``out_row [B, 5]``, row
         stride ``out_row.stride(0)``) for :meth:`step_fused` of stroke step+1.
         ``forced [B, 5]`` fp32 (any row stride) with ``nforced [B]`` int32: rows
         with ``step < nforced[b]`` take ``forced[b]`` as their stroke instead of
-        the draw (``csrc/mdn_sample.h``)."""
+        the draw (``csrc/mdn_sample.h``). ``temps [B]`` fp32: row b samples at
+        ``temps[b]`` instead of ``temp``."""
         s = DecodeSample()
         s.active = 1
         s.zs, s.ldz, s.nslab, s.slab = self.ZS.data_ptr(), 128, self.S_o, self.B * 128
@@ -332,6 +334,9 @@ class HyperStepDecoder:
             assert forced.dtype == torch.float32 and forced.shape == (self.B, 5) and forced.stride(1) == 1
             assert nforced.dtype == torch.int32 and nforced.shape == (self.B,) and nforced.stride(0) == 1
             s.forced, s.ld_forced, s.nforced = forced.data_ptr(), forced.stride(0), nforced.data_ptr()
+        if temps is not None:
+            assert temps.dtype == torch.float32 and temps.shape == (self.B,) and temps.stride(0) == 1
+            s.temps = temps.data_ptr()
         return s
 
     @torch.no_grad()

@@ -193,7 +193,28 @@ def check_prefix(name: str, prefix: torch.Tensor, prefix_len, B: int, N: int, de
     return prefix, plen
 
 
-def mdn_sample_torch(zh: torch.Tensor, M_: int, mode: int, temp: float, greedy: bool, fix_pen: bool,
+def check_temperature(name: str, temperature, B: int, dev) -> torch.Tensor:
+    """Validate the ``temperature=`` of a ``run()`` call (shared by
+    :class:`GraphDecoder` and the whole-sketch decoders of :mod:`.fused`): a
+    float, or a vector of ``B`` values, one per row; every value finite and
+    greater than 0 (greedy decoding is the ``greedy`` flag, not a temperature
+    of 0). Returns an fp32 ``[B]`` tensor on ``dev``; raises ``ValueError`` in
+    ``name``'s name."""
+    try:
+        t = torch.as_tensor(temperature).to(dev, torch.float32)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(name + ": temperature must be a float or a vector of %d floats" % B) from None
+    if t.dim() == 0:
+        t = t.expand(B)
+    if t.shape != (B,):
+        raise ValueError(name + ": temperature must be a float or a vector of %d floats, one per row" % B)
+    if not bool(torch.isfinite(t).all()) or not bool((t > 0).all()):
+        raise ValueError(name + ": temperatures must be finite and greater than 0 (greedy decoding is the greedy "
+                                "flag)")
+    return t.contiguous()
+
+
+def mdn_sample_torch(zh: torch.Tensor, M_: int, mode: int, temp, greedy: bool, fix_pen: bool,
                      seed, step: int, out_row: torch.Tensor, next_x: torch.Tensor, done: torch.Tensor,
                      params: Optional[torch.Tensor] = None, forced: Optional[torch.Tensor] = None,
                      nforced: Optional[torch.Tensor] = None) -> None:
@@ -205,13 +226,23 @@ def mdn_sample_torch(zh: torch.Tensor, M_: int, mode: int, temp: float, greedy: 
     emits ``forced[b]`` bit for bit instead of its draw, as ``out_row`` and as
     ``next_x``, takes its finished state from that row's stop column and
     never emits padding (``csrc/mdn_sample.h``). ``params`` keeps describing
-    the draw."""
+    the draw.
+
+    ``temp`` is a float, or an fp32 ``[B]`` tensor of per-row temperatures:
+    row b then uses ``temp[b]`` wherever the scalar is used, with the
+    reciprocal taken in fp32 per row as the kernel takes it (the scalar form
+    keeps its Python-float reciprocal)."""
     from ..models.cells import hash_uniform
     B = zh.shape[0]
     z = zh.float()
     u = hash_uniform(seed, _SAMPLE_STREAM, step, (B, 4), device=z.device)
     use_t = mode == 1 or step > 1
-    logits = z[:, 3:3 + M_] * ((1.0 / temp) if use_t else 1.0)
+    if torch.is_tensor(temp):      # per row: 1 / temps and temps broadcast over the row's columns, in fp32
+        tv = temp.to(z.device, torch.float32).reshape(B)
+        inv_t, temp = (1.0 / tv).unsqueeze(-1), tv
+    else:
+        inv_t = 1.0 / temp
+    logits = z[:, 3:3 + M_] * (inv_t if use_t else 1.0)
     pi = torch.softmax(logits, -1)
     ar = torch.arange(B, device=z.device)
     if greedy:
@@ -219,7 +250,7 @@ def mdn_sample_torch(zh: torch.Tensor, M_: int, mode: int, temp: float, greedy: 
     else:
         hit = torch.cumsum(pi, -1) >= u[:, 0:1]
         idx = torch.where(hit.any(-1), hit.float().argmax(-1), torch.full_like(ar, M_ - 1))
-    pt = (1.0 / temp) if (mode == 1 or (fix_pen and step > 1)) else 1.0
+    pt = inv_t if (mode == 1 or (fix_pen and step > 1)) else 1.0
     pp = torch.softmax(z[:, 0:3] * pt, -1)
     if greedy:
         pidx = pp.argmax(-1)
@@ -257,13 +288,16 @@ def mdn_sample_torch(zh: torch.Tensor, M_: int, mode: int, temp: float, greedy: 
         params.copy_(torch.stack([idx.float(), pidx.float(), s1, s2], -1))
 
 
-def mdn_sample_device(zh: torch.Tensor, M_: int, mode: int, temp: float, greedy: bool, fix_pen: bool,
+def mdn_sample_device(zh: torch.Tensor, M_: int, mode: int, temp, greedy: bool, fix_pen: bool,
                       seed: torch.Tensor, step: int, out_row: torch.Tensor, next_x: torch.Tensor,
                       done: torch.Tensor, params: Optional[torch.Tensor] = None,
                       forced: Optional[torch.Tensor] = None, nforced: Optional[torch.Tensor] = None) -> None:
     """``csrc/sampler.hip`` on a GPU tensor, :func:`mdn_sample_torch` elsewhere.
     ``forced [B, 5]`` (any row stride) with ``nforced [B]`` int32: rows with
-    ``step < nforced[b]`` emit ``forced[b]`` instead of their draw."""
+    ``step < nforced[b]`` emit ``forced[b]`` instead of their draw. ``temp``: a
+    float, or an fp32 ``[B]`` tensor of per-row temperatures."""
+    if torch.is_tensor(temp) and (temp.dtype != torch.float32 or temp.shape != (zh.shape[0],)):
+        raise ValueError("mdn_sample_device: per-row temperatures must be an fp32 [B] tensor")
     if (forced is None) != (nforced is None):
         raise ValueError("mdn_sample_device: forced and nforced go together")
     if zh.device.type != "cuda":
@@ -276,10 +310,24 @@ def mdn_sample_device(zh: torch.Tensor, M_: int, mode: int, temp: float, greedy:
     from ..utils import native
     lib = native.require_hip()
     import ctypes
+    B = zh.shape[0]
     if nforced is not None:
-        B = zh.shape[0]
         assert forced.dtype == torch.float32 and forced.shape == (B, 5) and forced.stride(1) == 1
         assert nforced.dtype == torch.int32 and nforced.shape == (B,) and nforced.stride(0) == 1
+    if torch.is_tensor(temp):
+        temps = temp.contiguous()      # the kernel indexes temps[b]; a strided view is copied
+        assert temps.device == zh.device
+        rc = lib.lib.skr_mdn_sample_temps(
+            zh.data_ptr(), zh.stride(0), B, M_, mode, 1.0, int(greedy), int(fix_pen), seed.data_ptr(), step,
+            out_row.data_ptr(), out_row.stride(0), next_x.data_ptr(), next_x.stride(0), done.data_ptr(),
+            params.data_ptr() if params is not None else None,
+            forced.data_ptr() if nforced is not None else None, forced.stride(0) if nforced is not None else 0,
+            nforced.data_ptr() if nforced is not None else None, temps.data_ptr(),
+            torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            raise RuntimeError("skr_mdn_sample_temps failed (%d)" % rc)
+        return
+    if nforced is not None:
         rc = lib.lib.skr_mdn_sample_forced(
             zh.data_ptr(), zh.stride(0), B, M_, mode, temp, int(greedy), int(fix_pen), seed.data_ptr(), step,
             out_row.data_ptr(), out_row.stride(0), next_x.data_ptr(), next_x.stride(0), done.data_ptr(),
@@ -338,6 +386,9 @@ class GraphDecoder:
         self.out = torch.zeros(batch, steps, 5, device=dev)
         self.done = torch.zeros(batch, dtype=torch.int32, device=dev)
         self.x0 = torch.zeros(batch, 5, device=dev)
+        # per-row temperatures: static like the prefix buffers below, read by every sampler call of every
+        # step path, so run(temperature=) never causes a recapture
+        self.temps = torch.full((batch,), self.temp, dtype=torch.float32, device=dev)
         if self.kind == "vae":
             self.x0[:, 2] = 1.0
             self.z = torch.zeros(batch, max(cfg.z_size, 1), device=dev)
@@ -416,18 +467,19 @@ class GraphDecoder:
                         smp = None if t == 0 else st.sample_args(
                             t - 1, r0, self.out[r0:r0 + n, t - 1], done, self.seed, self.Mx, self.mode, self.temp,
                             self.greedy, self.fix_pen, forced=self.prefix[r0:r0 + n, t - 1],
-                            nforced=self.nforced[r0:r0 + n])
+                            nforced=self.nforced[r0:r0 + n], temps=self.temps[r0:r0 + n])
                         st.step_fused(t, smp)
                     if t1 == N:
                         st.head()          # the last stroke: head + sampler
-                        rc = lib.skr_mdn_sample_slabs_forced(
+                        rc = lib.skr_mdn_sample_slabs_temps(
                             st.ZS.data_ptr(), 128, st.S_o, n * 128, st._w["bo"].data_ptr(), n, self.Mx, self.mode,
                             self.temp, int(self.greedy), int(self.fix_pen), self.seed.data_ptr(), N - 1, r0,
                             self.out[r0, N - 1].data_ptr(), ld_out, st.X.data_ptr(), 5, done.data_ptr(),
                             self.prefix[r0, N - 1].data_ptr(), ld_pre, self.nforced[r0:].data_ptr(),
+                            self.temps[r0:].data_ptr(),
                             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
                         if rc != 0:
-                            raise RuntimeError("skr_mdn_sample_slabs_forced failed (%d)" % rc)
+                            raise RuntimeError("skr_mdn_sample_slabs_temps failed (%d)" % rc)
                 continue
             with torch.cuda.stream(stream):
                 if t0 == 0:
@@ -438,14 +490,15 @@ class GraphDecoder:
                     nx = torch.empty(n, 5, device=self.dev)
 
                     def sample(zs, ldz, nslab, slab, bias, r0=r0, n=n, t=t, nx=nx):
-                        rc = lib.skr_mdn_sample_slabs_forced(
+                        rc = lib.skr_mdn_sample_slabs_temps(
                             zs.data_ptr(), ldz, nslab, slab, bias.data_ptr(), n, self.Mx, self.mode, self.temp,
                             int(self.greedy), int(self.fix_pen), self.seed.data_ptr(), t, r0,
                             self.out[r0, t].data_ptr(), ld_out, nx.data_ptr(), 5, self.done[r0:].data_ptr(),
                             self.prefix[r0, t].data_ptr(), ld_pre, self.nforced[r0:].data_ptr(),
+                            self.temps[r0:].data_ptr(),
                             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
                         if rc != 0:
-                            raise RuntimeError("skr_mdn_sample_slabs_forced failed (%d)" % rc)
+                            raise RuntimeError("skr_mdn_sample_slabs_temps failed (%d)" % rc)
                     st.step(x, t, sample)
                     x = nx
                 cy["x%d" % i] = x
@@ -486,7 +539,7 @@ class GraphDecoder:
                 zh, state = model.step(x, state)
             nx = torch.empty(B, 5, device=self.dev)
             forced = (self.prefix[:, t], self.nforced) if self.kind == "vae" else (None, None)
-            mdn_sample_device(zh.contiguous(), self.Mx, self.mode, self.temp, self.greedy, self.fix_pen, self.seed, t,
+            mdn_sample_device(zh.contiguous(), self.Mx, self.mode, self.temps, self.greedy, self.fix_pen, self.seed, t,
                               self.out[:, t], nx, self.done, None, *forced)
             x = nx
         cy["x"], cy["state"] = x, state
@@ -502,8 +555,14 @@ class GraphDecoder:
 
     @torch.no_grad()
     def run(self, seed: int = 0, z: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
-            prefix: Optional[torch.Tensor] = None, prefix_len: Optional[torch.Tensor] = None):
+            prefix: Optional[torch.Tensor] = None, prefix_len: Optional[torch.Tensor] = None,
+            temperature=None):
         """Returns ``(strokes [B, N, 5], lengths [B])``.
+
+        ``temperature``: a float, or a vector of B values (row b samples at
+        ``temperature[b]``), for this run only; None is the constructor's
+        value. It fills a static buffer the captured graphs read, so a
+        temperature never causes a recapture.
 
         ``prefix [B, P, 5]`` with ``prefix_len [B]`` (default P for every row;
         VAE models only) completes sketches: stroke t of row b is
@@ -512,6 +571,10 @@ class GraphDecoder:
         :mod:`.fused`). The prefix is copied into static buffers the captured
         graphs read, so it never causes a recapture, and a later run without
         one is a plain decode."""
+        if temperature is None:
+            self.temps.fill_(self.temp)
+        else:
+            self.temps.copy_(check_temperature("GraphDecoder.run", temperature, self.B, self.dev))
         if prefix is not None or prefix_len is not None:
             if self.kind != "vae":
                 raise ValueError("GraphDecoder.run: stroke prefixes need a VAE model")
