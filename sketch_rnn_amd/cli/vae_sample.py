@@ -23,7 +23,14 @@ temperature, all in one batch with a temperature per row, and lays the grid
 out with one line per latent and the temperatures as its columns (after the
 original in ``reconstruct``).
 
-Writes a stroke-3 SVG grid.
+Writes a stroke-3 SVG grid. ``--png PATH`` writes the same grid (the same
+sketches, order and columns) as a PNG of ``--png_size`` pixels per sketch,
+rasterised on the model's device by ``ops.raster.rasterize``. ``--mode
+reconstruct --raster_iou`` rasterises each original in its fitted frame and
+its reconstructions in that same frame, prints the mean
+``render.raster.soft_iou`` per decoded column and writes the per-sketch
+values to ``<out>.iou.json``; with ``--device_sampler`` on a GPU the decoded
+``[rows, N, 5]`` tensor is rasterised where it lies.
 ``--device_sampler`` decodes the whole grid in parallel through the
 HIP-graph decoder; with ``--fused`` a plain ``lstm`` or ``layer_norm``
 decoder of size 256 or 512 runs through its whole-sketch kernel
@@ -88,9 +95,23 @@ def main(argv=None) -> int:
     p.add_argument("--completions", type=int, default=1, help="complete: endings generated per prefix")
     p.add_argument("--z_from", choices=["prefix", "full", "prior"], default="prefix",
                    help="complete: latent of a conditional model (encode the prefix, the whole sketch, or draw it)")
+    p.add_argument("--png", default=None, metavar="PATH",
+                   help="also write the grid as a PNG: the same sketches in the same order and columns as the SVG, "
+                        "rasterised on the model's device")
+    p.add_argument("--png_size", type=int, default=64, help="--png / --raster_iou: pixels per sketch edge")
+    p.add_argument("--png_width", type=float, default=1.0, help="--png / --raster_iou: stroke width in pixels")
+    p.add_argument("--raster_iou", action="store_true",
+                   help="reconstruct: rasterise each original in its fitted frame and its reconstructions in the "
+                        "same frame, print the mean soft IoU per decoded column and write the per-sketch values "
+                        "to <out>.iou.json")
     a = p.parse_args(argv)
     if a.fused and not a.device_sampler:
         p.error("--fused needs --device_sampler")
+    if a.raster_iou and a.mode != "reconstruct":
+        p.error("--raster_iou works in the mode reconstruct")
+    if (a.png or a.raster_iou) and not (1 <= a.png_size <= 512 and math.isfinite(a.png_width) and a.png_width > 0
+                                        and a.png_size > 4):
+        p.error("--png_size must be in 5..512 and --png_width greater than 0")
     from_data = a.mode in ("reconstruct", "complete")
     temps = None
     if a.temperatures is not None:
@@ -175,6 +196,7 @@ def main(argv=None) -> int:
         row_temps = np.tile(np.asarray(temps, np.float64), a.n)
     rows = len(labels)
     sketches = []
+    s_dev = None                      # the decoded [rows, N, 5] tensor where a GPU device sampler left it
     if a.fused and not device.startswith("cuda"):
         print("--fused: no GPU device, sampling on the host")
     if a.device_sampler and (device.startswith("cuda") or from_data or temps is not None):
@@ -201,6 +223,8 @@ def main(argv=None) -> int:
             dec = GraphDecoder(model, rows, cfg.max_seq_len, a.temperature, a.greedy, fp8=a.fp8)
             s, _ = dec.run(seed=a.seed, z=zt, labels=lt, **pre_kw)
         sketches = [to_normal_strokes(x) for x in s.cpu().numpy()]
+        if device.startswith("cuda"):
+            s_dev = s
     else:
         for k in range(rows):
             z = torch.as_tensor(zs[k:k + 1], dtype=torch.float32, device=device)
@@ -209,12 +233,44 @@ def main(argv=None) -> int:
             s5, _ = sample_vae(model, cfg.max_seq_len, temp_k, a.greedy, z=z, label=int(labels[k]), rng=rng,
                                prefix=pre_k)
             sketches.append(to_normal_strokes(s5))
+    def batch3(sk):
+        """Stroke-3 lists padded into one [n, N, 3] batch on the model's device, with their lengths."""
+        x = np.zeros((len(sk), max([len(x_) for x_ in sk] + [1]), 3), np.float32)
+        for i, x_ in enumerate(sk):
+            x[i, :len(x_)] = x_
+        return (torch.as_tensor(x, device=device),
+                torch.as_tensor([len(x_) for x_ in sk], dtype=torch.int64, device=device))
+
+    if a.raster_iou:
+        import json
+        from ..ops.raster import rasterize
+        from ..render.raster import soft_iou
+        orig, frame = rasterize(*batch3(shown), size=a.png_size, width=a.png_width)
+        frame = frame.repeat_interleave(group, dim=0)
+        if s_dev is not None:   # the decoder's output where it lies: no host round trip
+            dec, _ = rasterize(s_dev.float(), None, size=a.png_size, width=a.png_width, frame=frame)
+        else:
+            dec, _ = rasterize(*batch3(sketches), size=a.png_size, width=a.png_width, frame=frame)
+        iou = soft_iou(orig.repeat_interleave(group, dim=0), dec).view(a.n, group).cpu()
+        cols = temps if temps is not None else [a.temperature]
+        print("raster IoU (%d sketches, %d px): %s" % (a.n, a.png_size, "  ".join(
+            "T=%g %.4f" % (t, m) for t, m in zip(cols, iou.mean(0).tolist()))))
+        with open(a.out + ".iou.json", "w") as f:
+            json.dump({"size": a.png_size, "width": a.png_width, "temperatures": cols,
+                       "mean": iou.mean(0).tolist(), "iou": iou.tolist()}, f)
     if shown is not None:       # each data sketch (or its prefix) followed by what was decoded from it
         sketches = [x for i, d in enumerate(shown) for x in [d] + sketches[i * group:(i + 1) * group]]
-    if temps is not None:       # one line per latent
-        grid_strokes3(sketches, a.out, maxcol=len(sketches) // a.n)
+    maxcol = len(sketches) // a.n if temps is not None else 5      # --temperatures: one line per latent
+    if temps is not None:
+        grid_strokes3(sketches, a.out, maxcol=maxcol)
     else:
         grid_strokes3(sketches, a.out)
+    if a.png:
+        from ..ops.raster import rasterize
+        from ..render.png import grid_png
+        images, _ = rasterize(*batch3(sketches), size=a.png_size, width=a.png_width)
+        grid_png(images, a.png, maxcol=maxcol)
+        print("wrote %s (%d sketches, %d px each)" % (a.png, len(sketches), a.png_size))
     print("wrote %s (%d sketches)" % (a.out, len(sketches)))
     return 0
 

@@ -247,6 +247,15 @@ class HeadScore(C.Structure):
     ]
 
 
+class RasterArgs(C.Structure):
+    """Mirror of ``RasterArgs`` in csrc/raster.hip (stroke batches to ink images)."""
+    _fields_ = [
+        ("strokes", _p), ("lengths", _p), ("frame_in", _p), ("frame", _p), ("seg", _p), ("count", _p), ("out", _p),
+        ("B", _i), ("N", _i), ("D", _i), ("S", _i),
+        ("width", _f), ("pad", _f), ("cull", _i), ("b0", _i),
+    ]
+
+
 class DecLayer(C.Structure):
     """Mirror of ``DecLayer`` in csrc/decode_ref.hip (fused whole-sketch decoder)."""
     _fields_ = [
@@ -502,6 +511,8 @@ class HipLib:
         lib.skr_mdn_head_dw.restype = _i
         lib.skr_mdn_head_score.argtypes = [C.POINTER(HeadScore), _p]
         lib.skr_mdn_head_score.restype = _i
+        lib.skr_raster.argtypes = [C.POINTER(RasterArgs), _p]
+        lib.skr_raster.restype = _i
         lib.skr_hyper_mod_fwd.argtypes = [_p, _i64, _p, _p, _p, _p, _i64, _i, _p, _p, _p, _p, _i, _i, _i,
                                           C.POINTER(ModDecode), _p]
         lib.skr_hyper_mod_fwd.restype = _i
@@ -527,6 +538,7 @@ class HipLib:
                           ("skr_mdn_head_dx_args_size", HeadDx),
                           ("skr_mdn_head_dw_args_size", HeadDw),
                           ("skr_mdn_head_score_args_size", HeadScore),
+                          ("skr_raster_args_size", RasterArgs),
                           ("skr_decode_ref_args_size", DecArgs),
                           ("skr_decode_vae_args_size", DecVaeArgs),
                           ("skr_decode_vae_ln_args_size", DecVaeLnArgs),
