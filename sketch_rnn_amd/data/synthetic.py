@@ -61,3 +61,36 @@ def synthetic_reference_corpus(n: int, seed: int = 0, max_len: int = 120) -> Lis
         r[-1, 3] = 1.0
         out.append(r)
     return out
+
+
+def synthetic_raw_corpus(n: int, seed: int = 0, mean_points: int = 600, max_points: int = 2048) -> List[np.ndarray]:
+    """Stroke-3 sketches that look like raw pen traces: the synthetic sketches
+    scaled up, with every pen-down segment subdivided into steps of 1-3 px and
+    the inner points jittered by -1, 0 or 1 px. Coordinates are integers;
+    about ``mean_points`` rows per sketch, at most ``max_points`` (a longer
+    trace is cut there), and sketch 0 has exactly ``max_points``."""
+    base, _ = synthetic_corpus(n, seed=seed, max_len=250, include_max=False)
+    rng = np.random.RandomState(seed + 1)
+    out = []
+    for i, s in enumerate(base):
+        want = max_points * 2 if i == 0 else int(np.clip(rng.gamma(4.0, mean_points / 4.0), 16, max_points))
+        P = np.cumsum(s[:, 0:2].astype(np.float64), axis=0)
+        A = np.concatenate([np.zeros((1, 2)), P[:-1]], axis=0)
+        down = np.concatenate([[False], s[:-1, 2] < 0.5])
+        path = float(np.sqrt(((P - A) ** 2).sum(axis=1))[down].sum())
+        f = max(1.0, 1.75 * want / max(path, 1.0))            # a step is 1-3 px: about 1.75 px per row
+        A, B = np.round(A * f), np.round(P * f)
+        seg = np.sqrt(((B - A) ** 2).sum(axis=1))
+        k = np.where(down, np.maximum(1, np.round(seg / rng.uniform(1.0, 3.0, size=len(s)))), 1).astype(np.int64)
+        idx = np.repeat(np.arange(len(s)), k)
+        j = np.arange(int(k.sum())) - np.repeat(np.cumsum(k) - k, k) + 1          # 1 .. k within a segment
+        last = j == k[idx]
+        pts = np.round(A[idx] + (B - A)[idx] * (j / k[idx])[:, None])
+        pts += np.where(last[:, None], 0, rng.randint(-1, 2, size=pts.shape))
+        rows = np.zeros((len(pts), 3), np.float32)
+        rows[:, 0:2] = pts - np.concatenate([np.zeros((1, 2)), pts[:-1]], axis=0)
+        rows[:, 2] = np.where(last, s[idx, 2], 0.0)
+        rows = rows[:max_points]
+        rows[-1, 2] = 1.0
+        out.append(rows)
+    return out

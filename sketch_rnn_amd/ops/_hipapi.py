@@ -256,6 +256,15 @@ class RasterArgs(C.Structure):
     ]
 
 
+class RdpArgs(C.Structure):
+    """Mirror of ``RdpArgs`` in csrc/simplify.hip (RDP tolerances and simplified batches)."""
+    _fields_ = [
+        ("strokes", _p), ("lengths", _p), ("epsilon", _p), ("tol", _p), ("out", _p), ("new_lengths", _p),
+        ("eps_used", _p), ("rounds", _p),
+        ("B", _i), ("N", _i), ("D", _i), ("max_len", _i),
+    ]
+
+
 class DecLayer(C.Structure):
     """Mirror of ``DecLayer`` in csrc/decode_ref.hip (fused whole-sketch decoder)."""
     _fields_ = [
@@ -513,6 +522,8 @@ class HipLib:
         lib.skr_mdn_head_score.restype = _i
         lib.skr_raster.argtypes = [C.POINTER(RasterArgs), _p]
         lib.skr_raster.restype = _i
+        lib.skr_rdp.argtypes = [C.POINTER(RdpArgs), _p]
+        lib.skr_rdp.restype = _i
         lib.skr_hyper_mod_fwd.argtypes = [_p, _i64, _p, _p, _p, _p, _i64, _i, _p, _p, _p, _p, _i, _i, _i,
                                           C.POINTER(ModDecode), _p]
         lib.skr_hyper_mod_fwd.restype = _i
@@ -539,6 +550,7 @@ class HipLib:
                           ("skr_mdn_head_dw_args_size", HeadDw),
                           ("skr_mdn_head_score_args_size", HeadScore),
                           ("skr_raster_args_size", RasterArgs),
+                          ("skr_rdp_args_size", RdpArgs),
                           ("skr_decode_ref_args_size", DecArgs),
                           ("skr_decode_vae_args_size", DecVaeArgs),
                           ("skr_decode_vae_ln_args_size", DecVaeLnArgs),
