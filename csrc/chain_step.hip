@@ -39,10 +39,14 @@ namespace {
 constexpr int kNs = 3;    // LDS ring depth of the tiles (the grouped launches' setting)
 constexpr int kBn = 64;   // N-tile width
 
-template <int NW>
+// VEC: the tile's 16-byte write-through epilogue (csrc/skinny_tile.h). On for the
+// HyperLSTM backward chain (16.65 -> 16.50 us per launch); off for the
+// LayerNorm-LSTM chains, where it measured slower than the dword stores
+// (vae_layernorm 8.94 / 8.95 vs 8.80 / 8.80 ms/step, profiles/r16/stores/ab.log).
+template <int NW, bool VEC>
 __device__ __forceinline__ void producer_tile(const GemmGroup& g, const ChainSync& cs, __hip_bfloat16* smem) {
     if (blockIdx.x == 0) chain_rotate(cs.counters, cs.n, cs.k);
-    group_tile<kBn, kNs, NW, true>(g, blockIdx.x, smem);
+    group_tile<kBn, kNs, NW, skr::ST_WT, VEC>(g, blockIdx.x, smem);
     chain_arrive(cs.counters + cs.k);
 }
 
@@ -57,7 +61,7 @@ __global__ __launch_bounds__(512) void chain_bwd_main_kernel(const GemmGroup g, 
     extern __shared__ __attribute__((aligned(16))) __hip_bfloat16 smem[];
     const int id = blockIdx.x;
     if (id < nprod) {
-        producer_tile<8>(g, cs, smem);
+        producer_tile<8, true>(g, cs, smem);
         return;
     }
     if constexpr (CL == 1) {
@@ -88,7 +92,7 @@ __global__ __launch_bounds__(512) void chain_ln_fwd_kernel(const GemmGroup g, co
             chain_arrive(cs.counters + cs.k);
             return;
         }
-        producer_tile<8>(g, cs, smem);
+        producer_tile<8, false>(g, cs, smem);
         return;
     }
     if (probe == 1 || __builtin_amdgcn_readfirstlane(threadIdx.x) >= NTR) return;   // (wave-uniform)
@@ -106,7 +110,7 @@ __global__ __launch_bounds__(512) void chain_ln_bwd_kernel(const GemmGroup g, co
             chain_arrive(cs.counters + cs.k);
             return;
         }
-        producer_tile<8>(g, cs, smem);
+        producer_tile<8, false>(g, cs, smem);
         return;
     }
     if (probe == 1 || __builtin_amdgcn_readfirstlane(threadIdx.x) >= NTR) return;

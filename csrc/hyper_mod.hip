@@ -31,6 +31,7 @@
 // MFMA stages, W_z L2-resident instead of the 12.6 MB folded P -- at 12.9 vs
 // 10.2 us per step, with a slower backward; profiles/r4/unfold_ab.txt.)
 #include "common.h"
+#include "store_policy.h"
 
 namespace {
 
@@ -62,6 +63,8 @@ struct ModDecode {
     const float* w5; int64_t ldw5;
     const float* zp; int64_t ldzp;
     int probe;                                // timing probe (skr_hyper_mod_set_probe; 0 = off), set by the host
+    int st;                                   // write-through stores (csrc/store_policy.h), set by the host:
+                                              // bit 0 the gate pre-activations g, bit 1 the saves (vec, rlp)
 };
 
 namespace {
@@ -186,6 +189,9 @@ __device__ __forceinline__ void mod_block(ModDecode dec, const __hip_bfloat16* _
     __syncthreads();
     // ---- epilogue (no loads left): 8 threads per row (lanes 8k..8k+7)
     const int ch = ul >> 4, cu = ul & 15;          // column tile half, column inside it
+    // (write-through arms, dec.st: buffer descriptors of this row block's outputs)
+    const __amdgpu_buffer_rsrc_t rg_ = skr::rsrc(gout, (int64_t)B * G * 4), rr_ = skr::rsrc(rlp, (int64_t)B * G * 2),
+                                 rv_ = skr::rsrc(vec, (int64_t)B * NV * 2);
 #pragma unroll
     for (int k = 0; k < RPT; ++k) {
         const int r = rg + k * (NTH / 8);
@@ -211,12 +217,25 @@ __device__ __forceinline__ void mod_block(ModDecode dec, const __hip_bfloat16* _
         s2 += __shfl_xor(s2, 4, 64);
         if (on) {
             const int64_t go = (int64_t)rr * G + q * H + u0 + ul;
-            *(f32x4*)(gout + go) = f32x4{g[0], g[1], g[2], g[3]};
-            if (rlp) *(u32x2*)(rlp + go) = u32x2{pack_bf(r4[k][0], r4[k][1]), pack_bf(r4[k][2], r4[k][3])};
             const int64_t vo = (int64_t)rr * NV + u0 + ul;
-            if (vec) {   // (null at inference)
-                *(u32x2*)(vec + vo + q * H) = u32x2{pack_bf(vx[0], vx[1]), pack_bf(vx[2], vx[3])};
-                *(u32x2*)(vec + vo + (4 + q) * H) = u32x2{pack_bf(vh[0], vh[1]), pack_bf(vh[2], vh[3])};
+            const u32x2 rl = {pack_bf(r4[k][0], r4[k][1]), pack_bf(r4[k][2], r4[k][3])};
+            const u32x2 px = {pack_bf(vx[0], vx[1]), pack_bf(vx[2], vx[3])}, ph = {pack_bf(vh[0], vh[1]), pack_bf(vh[2], vh[3])};
+            if (dec.st & 1)
+                skr::st16<skr::ST_WT>(rg_, (uint32_t)go * 4u, skr::u32x4{__float_as_uint(g[0]), __float_as_uint(g[1]),
+                                                                         __float_as_uint(g[2]), __float_as_uint(g[3])});
+            else *(f32x4*)(gout + go) = f32x4{g[0], g[1], g[2], g[3]};
+            if (dec.st & 2) {
+                if (rlp) skr::st8<skr::ST_WT>(rr_, (uint32_t)go * 2u, rl[0], rl[1]);
+                if (vec) {
+                    skr::st8<skr::ST_WT>(rv_, (uint32_t)(vo + q * H) * 2u, px[0], px[1]);
+                    skr::st8<skr::ST_WT>(rv_, (uint32_t)(vo + (4 + q) * H) * 2u, ph[0], ph[1]);
+                }
+            } else {
+                if (rlp) *(u32x2*)(rlp + go) = rl;
+                if (vec) {   // (null at inference)
+                    *(u32x2*)(vec + vo + q * H) = px;
+                    *(u32x2*)(vec + vo + (4 + q) * H) = ph;
+                }
             }
             // (the shift block 8..11 is not stored: the backward reads only
             // the x and h modulations -- d(shift) = dg needs no saved value)
@@ -304,6 +323,7 @@ SKR_API int skr_hyper_mod_fwd(const void* hh, int64_t ld_hh, const void* PlT, co
                               float* stats, int B, int H, int Hh, const ModDecode* dec, hipStream_t s) {
     ModDecode dz = dec ? *dec : ModDecode{};
     dz.probe = g_hm_probe;
+    dz.st = (skr_store_policy_of(skr::SC_STEP) == skr::ST_WT ? 1 : 0) | (skr_store_policy_of(skr::SC_SAVE) == skr::ST_WT ? 2 : 0);
     if (dz.x5 && (((uintptr_t)dz.w5 | (uintptr_t)dz.zp) & 15 || dz.ldw5 % 4 || dz.ldzp % 4)) return -4;
     if ((dz.x5 == nullptr && xh == nullptr) || hh == nullptr) return -3;
     if (B <= 0) return 0;

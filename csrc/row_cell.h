@@ -136,6 +136,12 @@ __device__ __forceinline__ void row_exchange(float (&v)[N], float* mine, float* 
 template <int NT, int V, int MOD, int DS, bool CHAIN = false>
 __device__ __forceinline__ void row_fwd_body(const FwdArgs& a, const int b, const uint32_t* chain_cnt = nullptr,
                                              uint32_t chain_target = 0, int* chain_err = nullptr) {
+    // Multiply-adds are fused per expression here, not wherever the optimiser
+    // finds a pair: with the file's default (fast) the step kernel and the
+    // chained kernel, compiled from this one body, fused different pairs and
+    // their outputs differed in the last bit (T = 3, B = 5, H = 512: 2.4e-07 of
+    // 0.93). With it they are bit-equal (tests/test_tile_store_gpu.py).
+#pragma clang fp contract(on)
     static_assert(!CHAIN || (V == 4 && MOD == 0), "chained forward row: MOD 0, 16-byte slab loads");
     constexpr int NW = NT / 64;
     __shared__ float lds[NW * 8];

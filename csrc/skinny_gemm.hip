@@ -34,14 +34,14 @@ using skr::BM;
 using skr::BK;
 using skr::wait_ahead;
 
-template <int BN, int NS, bool CBF16 = false>
+template <int BN, int NS, bool CBF16 = false, int ST = skr::ST_PLAIN>
 __global__ __launch_bounds__(256) void skinny_gemm_glds_kernel(
     const __hip_bfloat16* __restrict__ A, int64_t lda, int64_t a_batch,
     const __hip_bfloat16* __restrict__ Bt, int64_t ldb, int64_t b_batch,
     void* __restrict__ C, int64_t ldc, int64_t c_slab, int64_t c_batch, int M, int kslice) {
     extern __shared__ __attribute__((aligned(16))) __hip_bfloat16 smem[];
     const int64_t co = blockIdx.z * c_batch + blockIdx.y * c_slab;
-    glds_tile<BN, NS, CBF16>(A + blockIdx.z * a_batch, lda, Bt + blockIdx.z * b_batch, ldb,
+    glds_tile<BN, NS, CBF16, 4, ST>(A + blockIdx.z * a_batch, lda, Bt + blockIdx.z * b_batch, ldb,
                   CBF16 ? (void*)((__hip_bfloat16*)C + co) : (void*)((float*)C + co), ldc, M, blockIdx.x * BN,
                   (int64_t)blockIdx.y * kslice, kslice, smem);
 }
@@ -56,10 +56,10 @@ __global__ __launch_bounds__(256) void skinny_gemm_glds_kernel(
 // sums `start` (csrc/skinny_tile.h). A problem with M > 128 rows (M % 128 ==
 // 0: the wide decode of sample/hyper_step.py) runs as M / 128 row blocks
 // sharing B.
-template <int BN, int NS, int NW = 4>
+template <int BN, int NS, int NW = 4, int ST = skr::ST_PLAIN>
 __global__ __launch_bounds__(NW * 64) void skinny_gemm_group_kernel(const GemmGroup g) {
     extern __shared__ __attribute__((aligned(16))) __hip_bfloat16 smem[];
-    group_tile<BN, NS, NW>(g, blockIdx.x, smem);
+    group_tile<BN, NS, NW, ST>(g, blockIdx.x, smem);
 }
 
 // Grouped GEMM tiles + the rows of one backward LayerNorm cell step in ONE
@@ -69,14 +69,14 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_group_kernel(const GemmGr
 // slabs of this step -- beside dR_main W_h^T, which only the next step's
 // main cell reads: the 100-CU cell step hides under the weight stream
 // instead of being its own launch on the critical path.
-template <int BN, int NS, int DHS>
+template <int BN, int NS, int DHS, int ST = skr::ST_PLAIN>
 __global__ __launch_bounds__(256) void skinny_gemm_group_cellbwd_kernel(const GemmGroup g, const skr::BwdArgs cell) {
     extern __shared__ __attribute__((aligned(16))) __hip_bfloat16 smem[];
     if ((int)blockIdx.x < cell.B) {
         cell_bwd_body<256, 1, 1, true, 0, DHS>(cell, 0, blockIdx.x, 1);
         return;
     }
-    group_tile<BN, NS>(g, blockIdx.x - cell.B, smem);
+    group_tile<BN, NS, 4, ST>(g, blockIdx.x - cell.B, smem);
 }
 
 // fp32 operands (fp32 parity runs): the same LDS-DMA ring with K-tiles of
@@ -198,33 +198,50 @@ SKR_API int skr_gemm_set_nstage(int ns) {
     return 0;
 }
 
+// Store policy per output class (csrc/store_policy.h), read at launch time:
+// set it before a HIP graph capture, like the ring depth. Returns the
+// previous policy, or -2 for an unknown class / policy (policy < 0: query).
+static int g_store_policy[skr::kStoreClasses] = {skr::ST_WT, skr::ST_WT, skr::ST_WT};   // (measured: profiles/r16/stores/)
+SKR_API int skr_store_set_policy(int cls, int policy) {
+    if (cls < 0 || cls >= skr::kStoreClasses || policy >= skr::kStorePolicies) return -2;
+    const int prev = g_store_policy[cls];
+    if (policy >= 0) g_store_policy[cls] = policy;
+    return prev;
+}
+int skr_store_policy_of(int cls) { return g_store_policy[cls]; }
+
 namespace {
 
 template <typename K>
 void set_lds_attr(K k, size_t lds) {
-    // per instantiation, once (a HIP graph capture must not see the call twice)
-    static bool done = false;
-    if (!done) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        done = true;
-    }
+    // per kernel, once (a HIP graph capture must not see the call twice). Keyed
+    // by address: instantiations that differ only in a store policy share K.
+    static const void* done[64];
+    static int n = 0;
+    for (int i = 0; i < n; ++i)
+        if (done[i] == (const void*)k) return;
+    // (a full table would mean a call per launch, captures included: leave the
+    // kernel at its default instead, so a launch over 64 KiB fails loudly)
+    if (n == 64) return;
+    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    done[n++] = (const void*)k;
 }
 
-template <int BN, int NS, bool CBF16 = false>
+template <int BN, int NS, bool CBF16 = false, int ST = skr::ST_PLAIN>
 int launch_v2(dim3 grid, hipStream_t s, const void* A, int64_t lda, int64_t a_batch, const void* Bt, int64_t ldb,
               int64_t b_batch, void* C, int64_t ldc, int64_t c_slab, int64_t c_batch, int M, int kslice) {
     const size_t lds = (size_t)NS * (BM + BN) * BK * 2;
-    set_lds_attr(skinny_gemm_glds_kernel<BN, NS, CBF16>, lds);
-    hipLaunchKernelGGL((skinny_gemm_glds_kernel<BN, NS, CBF16>), grid, dim3(256), lds, s, (const __hip_bfloat16*)A,
+    set_lds_attr(skinny_gemm_glds_kernel<BN, NS, CBF16, ST>, lds);
+    hipLaunchKernelGGL((skinny_gemm_glds_kernel<BN, NS, CBF16, ST>), grid, dim3(256), lds, s, (const __hip_bfloat16*)A,
                        lda, a_batch, (const __hip_bfloat16*)Bt, ldb, b_batch, C, ldc, c_slab, c_batch, M, kslice);
     return SKR_CHECK_LAUNCH();
 }
 
-template <int BN, int NS, int NW = 4>
+template <int BN, int NS, int NW = 4, int ST = skr::ST_PLAIN>
 int launch_group(const GemmGroup& g, hipStream_t s) {
     const size_t lds = (size_t)NS * (BM + BN) * BK * 2;
-    set_lds_attr(skinny_gemm_group_kernel<BN, NS, NW>, lds);
-    hipLaunchKernelGGL((skinny_gemm_group_kernel<BN, NS, NW>), dim3(g.start[g.n]), dim3(NW * 64), lds, s, g);
+    set_lds_attr(skinny_gemm_group_kernel<BN, NS, NW, ST>, lds);
+    hipLaunchKernelGGL((skinny_gemm_group_kernel<BN, NS, NW, ST>), dim3(g.start[g.n]), dim3(NW * 64), lds, s, g);
     return SKR_CHECK_LAUNCH();
 }
 
@@ -243,10 +260,13 @@ SKR_API int skr_skinny_gemm_v2(const void* A, int64_t lda, int64_t a_batch, cons
     if (kslice % BK != 0 || lda % 8 != 0 || ldb % 8 != 0) return -3;
     if (((uintptr_t)A | (uintptr_t)Bt) & 15) return -4;
     const dim3 grid(N / bn, splits, batch);
-#define SKR_V2(BN_, NS_) launch_v2<BN_, NS_>(grid, s, A, lda, a_batch, Bt, ldb, b_batch, C, ldc, c_slab, c_batch, M, kslice)
+    const bool wt = g_store_policy[skr::SC_SLAB] == skr::ST_WT;
+#define SKR_V2A (grid, s, A, lda, a_batch, Bt, ldb, b_batch, C, ldc, c_slab, c_batch, M, kslice)
+#define SKR_V2(BN_, NS_) (wt ? launch_v2<BN_, NS_, false, skr::ST_WT> SKR_V2A : launch_v2<BN_, NS_> SKR_V2A)
     if (bn == 128) return g_nstage == 3 ? SKR_V2(128, 3) : SKR_V2(128, 4);
     return g_nstage == 3 ? SKR_V2(64, 3) : g_nstage == 6 ? SKR_V2(64, 6) : SKR_V2(64, 4);
 #undef SKR_V2
+#undef SKR_V2A
 }
 
 // As skr_skinny_gemm_v2 with a bf16 output (one slab: splits == 1), for
@@ -257,8 +277,11 @@ SKR_API int skr_skinny_gemm_v2_bf16out(const void* A, int64_t lda, int64_t a_bat
     if (M < 1 || M > BM || N % 64 != 0 || K % BK != 0 || lda % 8 != 0 || ldb % 8 != 0) return -2;
     if (((uintptr_t)A | (uintptr_t)Bt) & 15) return -4;
     const dim3 grid(N / 64, 1, batch);
-    return g_nstage == 3 ? launch_v2<64, 3, true>(grid, s, A, lda, a_batch, Bt, ldb, b_batch, C, ldc, 0, c_batch, M, K)
-                         : launch_v2<64, 4, true>(grid, s, A, lda, a_batch, Bt, ldb, b_batch, C, ldc, 0, c_batch, M, K);
+    // (the bf16 product is the HyperLSTM modulation vectors: a save, csrc/store_policy.h)
+#define SKR_V2B(NS_, ST_) launch_v2<64, NS_, true, ST_>(grid, s, A, lda, a_batch, Bt, ldb, b_batch, C, ldc, 0, c_batch, M, K)
+    if (g_store_policy[skr::SC_SAVE] == skr::ST_WT) return g_nstage == 3 ? SKR_V2B(3, skr::ST_WT) : SKR_V2B(4, skr::ST_WT);
+    return g_nstage == 3 ? SKR_V2B(3, skr::ST_PLAIN) : SKR_V2B(4, skr::ST_PLAIN);
+#undef SKR_V2B
 }
 
 // Grouped bf16 products (see skinny_gemm_group_kernel): each problem as
@@ -282,9 +305,11 @@ SKR_API int skr_skinny_gemm_group(const GemmProblem* probs, int n, int bn, hipSt
     // 128-wide tiles run on 8 waves (512 threads: wave w = row quarter w % 4 x
     // column half w / 4): the same per-wave work as two 64-wide 4-wave
     // workgroups, with the activation rows staged once for 128 columns
-    if (bn == 128) return g_nstage == 3 ? launch_group<128, 3, 8>(g, s) : launch_group<128, 4, 8>(g, s);
-    return g_nstage == 3 ? launch_group<64, 3>(g, s) : g_nstage == 6 ? launch_group<64, 6>(g, s)
-                                                                    : launch_group<64, 4>(g, s);
+    const bool wt = g_store_policy[skr::SC_SLAB] == skr::ST_WT;
+#define SKR_GR(BN_, NS_, NW_) (wt ? launch_group<BN_, NS_, NW_, skr::ST_WT>(g, s) : launch_group<BN_, NS_, NW_>(g, s))
+    if (bn == 128) return g_nstage == 3 ? SKR_GR(128, 3, 8) : SKR_GR(128, 4, 8);
+    return g_nstage == 3 ? SKR_GR(64, 3, 4) : g_nstage == 6 ? SKR_GR(64, 6, 4) : SKR_GR(64, 4, 4);
+#undef SKR_GR
 }
 
 // skr_skinny_gemm_group (64-wide tiles, 3-stage ring) plus one backward
@@ -313,10 +338,16 @@ SKR_API int skr_skinny_gemm_group_cellbwd(const GemmProblem* probs, int n, const
     for (int i = n + 1; i <= kMaxGroup; ++i) g.start[i] = g.start[n];
     const size_t lds = (size_t)3 * (BM + 64) * BK * 2;
     const dim3 grid(a.B + g.start[n]);
-#define SKR_GC(D)                                                                                           \
-    do {                                                                                                    \
-        set_lds_attr(skinny_gemm_group_cellbwd_kernel<64, 3, D>, lds);                                      \
-        hipLaunchKernelGGL((skinny_gemm_group_cellbwd_kernel<64, 3, D>), grid, dim3(256), lds, s, g, a);    \
+    const bool wt = g_store_policy[skr::SC_SLAB] == skr::ST_WT;
+#define SKR_GC1(D, ST_)                                                                                          \
+    do {                                                                                                         \
+        set_lds_attr(skinny_gemm_group_cellbwd_kernel<64, 3, D, ST_>, lds);                                      \
+        hipLaunchKernelGGL((skinny_gemm_group_cellbwd_kernel<64, 3, D, ST_>), grid, dim3(256), lds, s, g, a);    \
+    } while (0)
+#define SKR_GC(D)                         \
+    do {                                  \
+        if (wt) SKR_GC1(D, skr::ST_WT);   \
+        else SKR_GC1(D, skr::ST_PLAIN);   \
     } while (0)
     switch (dhs) {
         case 1: SKR_GC(1); break;
@@ -325,6 +356,7 @@ SKR_API int skr_skinny_gemm_group_cellbwd(const GemmProblem* probs, int n, const
         default: SKR_GC(64); break;
     }
 #undef SKR_GC
+#undef SKR_GC1
     return SKR_CHECK_LAUNCH();
 }
 

@@ -356,6 +356,7 @@ class ModDecode(C.Structure):
     HyperLSTM modulation kernel: the x-projection from the stroke)."""
     _fields_ = [
         ("xh_bf16", _i), ("x5", _p), ("w5", _p), ("ldw5", _i64), ("zp", _p), ("ldzp", _i64), ("probe", _i),
+        ("st", _i),
     ]
 
 
@@ -474,6 +475,8 @@ class HipLib:
         lib.skr_skinny_gemm_v2_bf16out.restype = _i
         lib.skr_gemm_set_nstage.argtypes = [_i]
         lib.skr_gemm_set_nstage.restype = _i
+        lib.skr_store_set_policy.argtypes = [_i, _i]
+        lib.skr_store_set_policy.restype = _i
         lib.skr_skinny_gemm_group.argtypes = [C.POINTER(GemmProblem), _i, _i, _p]
         lib.skr_skinny_gemm_group.restype = _i
         lib.skr_skinny_gemm_group_cellbwd.argtypes = [C.POINTER(GemmProblem), _i, C.POINTER(LstmBwdArgs), _p]

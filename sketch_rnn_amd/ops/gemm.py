@@ -447,12 +447,56 @@ def plan_splits(M: int, N: int, K: int, batch: int = 1, dtype: torch.dtype = _BF
     return best
 
 
+# Store policies of the per-step launches' outputs, one per output class
+# (csrc/store_policy.h; every policy stores the same bits): "plain", or "wt"
+# for write-through (sc1) stores that leave no dirty lines behind at the
+# kernel boundary. Read at launch time: set them before a graph capture.
+#   STORE_SLABS  the split-K slabs the skinny tiles write for the next launch
+#                (the chained launches' producers always store write-through:
+#                their rows read the slabs in the same launch)
+#   STORE_STEP   the modulation step's gate pre-activations
+#   STORE_SAVES  the modulation step's vectors and bf16 R (and the bf16-output
+#                product that writes the vectors when the step is not fused)
+# Measured on vae_large, same box, arms alternated (profiles/r16/stores/
+# ab.log): slabs "wt" 23.26 - 23.33 ms/step against 23.80 - 23.85 for
+# "plain" (23.70 - 23.75 for the dword epilogue before it); on top of that
+# 23.44 / 23.49 with both modulation classes plain, 23.35 / 23.33 with the
+# step outputs written through, 23.35 / 23.34 with the saves, 23.28 / 23.24
+# with both. (The cells' own stores have no policy: measured slower,
+# profiles/r16/stores/README.md.)
+STORE_SLABS = os.environ.get("SKR_STORE_SLABS", "wt")
+STORE_STEP = os.environ.get("SKR_STORE_STEP", "wt")
+STORE_SAVES = os.environ.get("SKR_STORE_SAVES", "wt")
+_STORE_POLICIES = {"plain": 0, "wt": 1}
+
+
+def _policy(name: str, value: str) -> int:
+    if value not in _STORE_POLICIES:
+        raise ValueError("ops.gemm.%s = %r: a store policy is one of %s" % (name, value, sorted(_STORE_POLICIES)))
+    return _STORE_POLICIES[value]
+
+
+def apply_store_policy(lib) -> None:
+    """Hand the three library-side classes to the kernel library (every
+    launch path calls this: the library keeps no setting of its own that
+    these attributes do not overwrite)."""
+    for cls, name in enumerate(("STORE_SLABS", "STORE_STEP", "STORE_SAVES")):
+        if lib.lib.skr_store_set_policy(cls, _policy(name, globals()[name])) < 0:
+            raise RuntimeError("skr_store_set_policy rejected class %d" % cls)
+
+
+def _ldc(out: torch.Tensor, N: int) -> int:
+    """Row stride of a slab buffer (a one-row dimension's stride means nothing)."""
+    return out.stride(-2) if out.shape[-2] > 1 else N
+
+
 def rec_gemm(a: torch.Tensor, bt: torch.Tensor, out: torch.Tensor, splits: int, nd: int = 1,
              bn: int = 0) -> torch.Tensor:
     """Per-step recurrent product with split-K partial slabs.
 
     ``a [nd*M, K]`` (row stride may exceed K), ``bt [nd, N, K]`` (B^T, i.e.
-    K-contiguous), ``out [S, nd*M, N]`` fp32 with ``S = max(splits, 1)``:
+    K-contiguous), ``out [S, nd*M, N]`` fp32 (row stride may exceed N) with
+    ``S = max(splits, 1)``:
     ``sum_s out[s] = a @ bt^T``. ``splits == 0`` selects the library path
     (one slab). The fused cell kernels sum the slabs while loading.
     """
@@ -471,16 +515,18 @@ def rec_gemm(a: torch.Tensor, bt: torch.Tensor, out: torch.Tensor, splits: int, 
         fn = lambda *args: f32(*args[:-2], args[-1])   # noqa: E731  (drop bn)
     else:
         fn = lib.lib.skr_skinny_gemm_v2
+        apply_store_policy(lib)
+    ldc = _ldc(out, N)
     if nd == 1 and M > 128 and M % 128:   # a partial last row block: the grouped kernel takes it
         _launch_group([(a, bt, out, splits)])
         return out
     if nd == 1 and M > 128:   # 128-row blocks as the kernel's batch dimension, sharing B
         mb = row_blocks(M)
-        rc = fn(a.data_ptr(), a.stride(0), 128 * a.stride(0), bt.data_ptr(), bt.stride(-2), 0, out.data_ptr(), N,
-                out.stride(0), 128 * N, 128, N, K, splits, mb, bn, torch.cuda.current_stream().cuda_stream)
+        rc = fn(a.data_ptr(), a.stride(0), 128 * a.stride(0), bt.data_ptr(), bt.stride(-2), 0, out.data_ptr(), ldc,
+                out.stride(0), 128 * ldc, 128, N, K, splits, mb, bn, torch.cuda.current_stream().cuda_stream)
     else:
         rc = fn(a.data_ptr(), a.stride(0), M * a.stride(0), bt.data_ptr(), bt.stride(-2), N * K if nd > 1 else 0,
-                out.data_ptr(), N, out.stride(0), M * N, M, N, K, splits, nd, bn,
+                out.data_ptr(), ldc, out.stride(0), M * ldc, M, N, K, splits, nd, bn,
                 torch.cuda.current_stream().cuda_stream)
     if rc != 0:
         raise RuntimeError("skr_skinny_gemm failed (%d) for M=%d N=%d K=%d S=%d" % (rc, M, N, K, splits))
@@ -495,6 +541,7 @@ def rec_gemm_bf16out(a: torch.Tensor, bt: torch.Tensor, out: torch.Tensor) -> to
     M, K = a.shape
     N = bt.shape[-2]
     assert out.dtype == _BF16 and out.shape[-1] == N and M <= 128
+    apply_store_policy(lib)
     rc = lib.lib.skr_skinny_gemm_v2_bf16out(a.data_ptr(), a.stride(0), 0, bt.data_ptr(), bt.stride(-2), 0,
                                             out.data_ptr(), out.stride(-2), 0, M, N, K, 1,
                                             torch.cuda.current_stream().cuda_stream)
@@ -530,11 +577,12 @@ def _launch_group(jobs) -> None:
     from ..utils import native
     from ._hipapi import GemmProblem
     lib = native.require_hip()
+    apply_store_policy(lib)
     probs = (GemmProblem * len(jobs))()
     for p, (a, bt, out, s) in zip(probs, jobs):
         N, K = bt.shape[-2], bt.shape[-1]
         p.A, p.lda, p.Bt, p.ldb = a.data_ptr(), a.stride(0), bt.data_ptr(), bt.stride(-2)
-        p.C, p.ldc, p.c_slab = out.data_ptr(), N, out.stride(0)
+        p.C, p.ldc, p.c_slab = out.data_ptr(), _ldc(out, N), out.stride(0)
         p.M, p.N, p.K, p.splits = a.shape[0], N, K, s
     rc = lib.lib.skr_skinny_gemm_group(probs, len(jobs), GROUP_BN, torch.cuda.current_stream().cuda_stream)
     if rc != 0:
@@ -548,7 +596,7 @@ def _problems(jobs):
         assert a.is_cuda and a.dtype == _BF16 and s >= 1 and a.shape[0] <= 1024
         N, K = bt.shape[-2], bt.shape[-1]
         p.A, p.lda, p.Bt, p.ldb = a.data_ptr(), a.stride(0), bt.data_ptr(), bt.stride(-2)
-        p.C, p.ldc, p.c_slab = out.data_ptr(), N, out.stride(0)
+        p.C, p.ldc, p.c_slab = out.data_ptr(), _ldc(out, N), out.stride(0)
         p.M, p.N, p.K, p.splits = a.shape[0], N, K, s
     return probs
 
@@ -561,6 +609,7 @@ def rec_gemm_group_cellbwd(jobs, cell_args) -> None:
     import ctypes
     from ..utils import native
     lib = native.require_hip()
+    apply_store_policy(lib)
     probs = _problems(jobs)
     rc = lib.lib.skr_skinny_gemm_group_cellbwd(probs, len(jobs), ctypes.byref(cell_args),
                                                torch.cuda.current_stream().cuda_stream)

@@ -119,6 +119,7 @@ def apply_hm_zgrid(lib) -> None:
     if HM_ZGRID != _ZGRID_SET[0]:
         lib.lib.skr_hyper_mod_set_zgrid(int(HM_ZGRID))
         _ZGRID_SET[0] = HM_ZGRID
+    gemm.apply_store_policy(lib)
 
 
 SAY_CAP = 2   # split-K ceiling of dR_hyp W_y^T (backward; see _HyperSeq.backward)
