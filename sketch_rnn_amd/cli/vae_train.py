@@ -42,6 +42,9 @@ def build_parser():
     p.add_argument("--resume", action="store_true")
     p.add_argument("--metrics", default=None)
     p.add_argument("--no_graph", action="store_true")
+    p.add_argument("--device_data", action="store_true",
+                   help="hold the datasets on the device and assemble every batch there (stateless shuffle "
+                        "and augmentation keyed by --seed and the step; no prefetch thread)")
     return p
 
 
@@ -86,6 +89,10 @@ def main(argv=None) -> int:
         torch.cuda.set_device(torch.device(device))
     dp.init_from_env(device=device)
     (train, valid, test), scale = make_datasets(cfg, a.data, a.synthetic, dp.rank())
+    if a.device_data:
+        from ..data.device_dataset import DeviceStrokeDataset
+        train, valid, test = (None if ds is None else DeviceStrokeDataset.from_dataset(ds, device, seed=cfg.seed)
+                              for ds in (train, valid, test))
     tr = VAETrainer(cfg, train, valid, test, device=device, save_dir=a.save_dir,
                     use_graph=False if a.no_graph else None, metrics_path=a.metrics, compute_dtype=a.dtype)
     if dp.rank() == 0:

@@ -265,6 +265,18 @@ class RdpArgs(C.Structure):
     ]
 
 
+class BatchArgs(C.Structure):
+    """Mirror of ``BatchArgs`` in csrc/batch.hip (training batches assembled on the device)."""
+    _fields_ = [
+        ("points", _p), ("offsets", _p), ("labels_in", _p), ("indices", _p), ("strokes", _p), ("lengths", _p),
+        ("labels", _p),
+        ("S", _i64), ("seed", _i64), ("step", _i64), ("row0", _i64), ("G", _i64),
+        ("prob", C.c_double), ("f", _f),
+        ("B", _i), ("Nmax", _i), ("kbits", _i),
+        ("s_shuffle", _u32), ("s_scale", _u32), ("s_drop", _u32),
+    ]
+
+
 class DecLayer(C.Structure):
     """Mirror of ``DecLayer`` in csrc/decode_ref.hip (fused whole-sketch decoder)."""
     _fields_ = [
@@ -527,6 +539,8 @@ class HipLib:
         lib.skr_raster.restype = _i
         lib.skr_rdp.argtypes = [C.POINTER(RdpArgs), _p]
         lib.skr_rdp.restype = _i
+        lib.skr_batch_assemble.argtypes = [C.POINTER(BatchArgs), _p]
+        lib.skr_batch_assemble.restype = _i
         lib.skr_hyper_mod_fwd.argtypes = [_p, _i64, _p, _p, _p, _p, _i64, _i, _p, _p, _p, _p, _i, _i, _i,
                                           C.POINTER(ModDecode), _p]
         lib.skr_hyper_mod_fwd.restype = _i
@@ -554,6 +568,7 @@ class HipLib:
                           ("skr_mdn_head_score_args_size", HeadScore),
                           ("skr_raster_args_size", RasterArgs),
                           ("skr_rdp_args_size", RdpArgs),
+                          ("skr_batch_args_size", BatchArgs),
                           ("skr_decode_ref_args_size", DecArgs),
                           ("skr_decode_vae_args_size", DecVaeArgs),
                           ("skr_decode_vae_ln_args_size", DecVaeLnArgs),

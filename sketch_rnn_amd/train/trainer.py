@@ -24,6 +24,7 @@ import torch
 
 from ..ckpt import checkpoint as ckpt
 from ..config import RefConfig, VAEConfig
+from ..data.device_dataset import DeviceStrokeDataset
 from ..models.reference import SketchRNN
 from ..models.vae import SketchVAE
 from ..ops import gemm
@@ -217,6 +218,9 @@ class VAETrainer:
         self.cfg = cfg
         self.train_set, self.valid_set, self.test_set = train_set, valid_set, test_set
         self.device = torch.device(device)
+        for ds in (train_set, valid_set, test_set):
+            if isinstance(ds, DeviceStrokeDataset) and ds.device.type != self.device.type:
+                raise ValueError("a DeviceStrokeDataset on %s cannot feed a trainer on %s" % (ds.device, self.device))
         self.rank, self.world = dp.rank(), dp.world_size()
         self.model = SketchVAE(cfg).to(self.device)
         from .. import ops
@@ -427,6 +431,16 @@ class VAETrainer:
             self.opt.step()
         return out
 
+    def _static_inputs(self):
+        """The captured step's input buffers ``(strokes, lengths, labels)``, or
+        ``None`` before the capture and without a graph. A batch written into
+        them is replayed without a copy (``GraphedStep`` / ``GraphedPhases``
+        skip an input that aliases its static buffer)."""
+        if not self.use_graph or self._graph is None:
+            return None
+        st = self._graph.static
+        return st["strokes"], st["lengths"], st["labels"]
+
     def batch_to_device(self, batch):
         s, l, c = batch
         return (_to_device(s, self.device), _to_device(l, self.device, torch.int64),
@@ -463,8 +477,9 @@ class VAETrainer:
         for b in range(n):
             batch = dataset.get_batch(b)
             s, l, c = self.batch_to_device(batch)
+            longest = int(batch[1].max()) if torch.is_tensor(batch[1]) else int(np.max(batch[1]))
             out = self.model.score(s, l, c if self.cfg.num_classes > 0 else None, samples=samples, seed=seed + b,
-                                   max_len=int(np.max(batch[1])))
+                                   max_len=longest)
             keys = keys or list(out)
             rows.append(torch.stack([out[k].to(torch.float64) for k in keys]).cpu().numpy())
         if not rows:
@@ -479,8 +494,8 @@ class VAETrainer:
         pf = getattr(self, "_prefetch", None)
         if pf is not None and pf.consumed_state is not None:
             extra["data"] = pf.consumed_state     # batches still queued are regenerated on resume
-        elif hasattr(self.train_set, "state_dict"):
-            extra["data"] = self.train_set.state_dict()
+        elif hasattr(self.train_set, "state_dict") and not isinstance(self.train_set, DeviceStrokeDataset):
+            extra["data"] = self.train_set.state_dict()     # device-assembled batches are stateless: nothing to store
         return ckpt.save_checkpoint(self.save_dir, self.step, self.model, self.opt, self.cfg, extra=extra)
 
     def resume(self) -> bool:
@@ -493,7 +508,8 @@ class VAETrainer:
             return False
         self.step, extra, _ = ckpt.load_checkpoint(path, self.model, self.opt)
         self.seed.fill_(int(extra.get("seed", self.step * self.world)) + self.rank)   # saved by rank 0
-        if "data" in extra and hasattr(self.train_set, "load_state_dict"):
+        if "data" in extra and hasattr(self.train_set, "load_state_dict") \
+                and not isinstance(self.train_set, DeviceStrokeDataset):
             self.train_set.load_state_dict(extra["data"])
             if self.rank:
                 self.train_set.aug_rng.seed((self.cfg.seed * 7919 + 1 + self.rank + self.step) % (2 ** 32))
@@ -503,10 +519,13 @@ class VAETrainer:
               prefetch: bool = True):
         """Step loop. ``prefetch``: batches are built ``2`` ahead on a
         background thread into pinned host memory (:mod:`..data.prefetch`);
-        the same batches in the same order as without it."""
+        the same batches in the same order as without it. A
+        :class:`~..data.device_dataset.DeviceStrokeDataset` assembles each
+        batch on the device, a function of ``(cfg.seed, step)`` alone, straight
+        into the captured step's input buffers: no thread, nothing to rewind."""
         from ..data.prefetch import Prefetcher
         self._prefetch = None
-        if prefetch:
+        if prefetch and not isinstance(self.train_set, DeviceStrokeDataset):
             self._prefetch = Prefetcher(lambda: self.train_set.random_batch(self.rank, self.world),
                                         getattr(self.train_set, "state_dict", None))
         try:
@@ -531,11 +550,18 @@ class VAETrainer:
         # every rank's points (DP): summed on the device from each step's reduced arena tail
         valid_glob = torch.zeros((), dtype=torch.float64, device=self.device)
         n_int = 0       # steps since the last log line (resume / repeated train() safe)
+        dev_data = isinstance(self.train_set, DeviceStrokeDataset)
+        valid_dev = torch.zeros((), dtype=torch.float64, device=self.device)   # device-assembled batches' points
         while self.step < num_steps:
             with phase("data", self.host_times):
-                raw = pf.get() if pf is not None else self.train_set.random_batch(self.rank, self.world)
-                valid += float(np.asarray(raw[1]).sum())
-                batch = self.batch_to_device(raw)
+                if dev_data:
+                    # one launch in front of the replay, into the step graph's own inputs once they exist
+                    batch = self.train_set.random_batch(self.step, self.rank, self.world, out=self._static_inputs())
+                    valid_dev.add_(batch[1].sum())
+                else:
+                    raw = pf.get() if pf is not None else self.train_set.random_batch(self.rank, self.world)
+                    valid += float(np.asarray(raw[1]).sum())
+                    batch = self.batch_to_device(raw)
             with phase("step", self.host_times):
                 out = self.train_step(*batch)
             if self.reducer is not None:
@@ -552,11 +578,12 @@ class VAETrainer:
                     valid_all = float(valid_glob)           # summed per step from the reduced tails
                 else:
                     vals = {k: float(v) for k, v in out.items()}
-                    valid_all = valid                       # one rank: this rank's batches
+                    valid_all = float(valid_dev) if dev_data else valid     # one rank: this rank's batches
                 dt = (time.time() - t0) / n_int
                 t0 = time.time()
                 valid = 0.0
                 valid_glob.zero_()
+                valid_dev.zero_()
                 if self.rank == 0:
                     self.log("step: %d, lr: %.6f, klw: %0.4f, cost: %.4f, recon: %.4f, kl: %.4f, time/step: %.4f" % (
                         self.step, self.opt.lr, schedules.kl_weight(cfg, self.step - 1), vals["cost"],
