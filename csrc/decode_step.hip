@@ -39,9 +39,75 @@ struct DecodeSample {
     const float* forced; int64_t ld_forced;   // rows with step < nforced[b] emit forced[b] instead of
     const int* nforced;                // their draw (mdn_sample.h; nullptr: none)
     const float* temps;                // [B] per-row temperature in place of temp (nullptr: temp)
+    // slot map (nullptr: none). With it `step` is the launch's index inside the replayed chunk, out_row
+    // the base of out [jobs][nsteps][5] with ld_out its job stride, temps is required and forced is not taken.
+    const int* job;                    // [B] job of slot b (< 0: none yet)
+    const int* pos;                    // [B] local index of the stroke the chunk's first launch draws (-1: fresh slot)
+    const int* first_row;              // [1] hash row of job 0; without the map (nullptr: 0): added to row0
+    int nsteps;                        // strokes per job: the draw of stroke nsteps - 1 ends the job
 };
 
 namespace {
+
+// The slot map's loads beside the temperature's, held across wave 0 like
+// mdn_forced_load's value: lane 6 temps[b], lane 7 job[b], lane 8 pos[b],
+// lane 9 *first_row. One per-lane vector load; nothing waits for it until
+// the gathers after the slab fold.
+__device__ inline float map_load(const DecodeSample& s, int b) {
+    const int lane = threadIdx.x;
+    float v = 0.f;
+    if ((lane >= 6) & (lane <= 9)) {
+        const float* t6 = s.temps + b;
+        const float* t7 = reinterpret_cast<const float*>(s.job + b);
+        const float* t8 = reinterpret_cast<const float*>(s.pos + b);
+        const float* t9 = reinterpret_cast<const float*>(s.first_row);
+        v = *(lane == 6 ? t6 : lane == 7 ? t7 : lane == 8 ? t8 : t9);
+    }
+    return v;
+}
+
+// Wave 0 of slot b after the fold (every lane active). A fresh slot
+// (p < 0) draws nothing and feeds the start token; otherwise stroke p of the
+// slot's job is drawn as the plain decode draws stroke p of row
+// first_row + job, stored unless the slot had finished (the output buffer
+// holds the padding row already), and the draw of stroke nsteps - 1 ends
+// the job whatever its pen state.
+__device__ inline void map_sample(const DecodeSample& s, float fv, const float* zrow, float* x, float* xr, int b) {
+    const int lane = threadIdx.x;
+    const int bits = __float_as_int(fv);
+    const int jb = __builtin_amdgcn_readlane(bits, 7);
+    const int p = __builtin_amdgcn_readlane(bits, 8) + (int)s.step;
+    const int row = __builtin_amdgcn_readlane(bits, 9) + jb;
+    if (p < 0) {
+        if (lane < 5) {
+            const float v = lane == 2 ? 1.f : 0.f;
+            x[b * 5 + lane] = v;
+            xr[lane] = v;
+        }
+        return;
+    }
+    const uint32_t key = skr::hash_key(*s.seed, 0x5A3Du, (uint32_t)p);
+    const float tb = skr::mdn_temp_gather(fv, s.temps, s.temp);
+    const skr::MdnDraw d =
+        skr::mdn_sample_wave(zrow, s.M, s.mode, tb, 1.f / tb, s.greedy, s.fix_pen, key, (uint32_t)row, (uint32_t)p);
+    if (lane == 0) {
+        // mdn_emit_row without forced rows, its padding left to the pre-filled buffer: the draw ends at
+        // the same barrier (mdn_sample.h), so it keeps the bits it has in every other kernel
+        const int was = s.done[b];
+        const int stop_col = s.mode == 1 ? 4 : 3;
+        const bool store = was == 0 && jb >= 0 && p < s.nsteps;
+        float* op = s.out_row + (int64_t)jb * s.ld_out + (int64_t)p * 5;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            float v = d.row[k];
+            asm volatile("" : "+v"(v));
+            if (store) op[k] = v;
+            x[b * 5 + k] = v;
+            xr[k] = v;
+        }
+        if (was == 0 && (d.pidx + 2 == stop_col || p >= s.nsteps - 1)) s.done[b] = 1;
+    }
+}
 
 // One row per workgroup, unit u = threadIdx.x (H <= 256). Every global load of
 // the cell (R slabs, z projection, stroke weights, LayerNorm parameters,
@@ -49,7 +115,7 @@ namespace {
 // stroke -- so its latency overlaps the head-slab fold and the draw. The
 // arithmetic is cell_fwd_body<256, 1, NS, true, 0>'s (csrc/cell_fwd_body.h)
 // with the x-projection formed from the stroke, term for term.
-template <int NS>
+template <int NS, bool MAP>
 __global__ __launch_bounds__(256) void decode_hyper_cell(const FwdArgs a, const DecodeSample s, float* __restrict__ x,
                                                          const float* __restrict__ w5, int64_t ldw5) {
     __shared__ float part[4][256];
@@ -75,15 +141,20 @@ __global__ __launch_bounds__(256) void decode_hyper_cell(const FwdArgs a, const 
     const float lcg = a.lnc_g[u], lcb = a.lnc_b[u];
     const float cp = a.c_prev[(int64_t)b * H + u];
     const float* temps = s.active ? s.temps : nullptr;
-    const float fv = skr::mdn_forced_load(s.forced, s.ld_forced, s.active ? s.nforced : nullptr, temps, b);
+    float fv;
+    if constexpr (MAP) fv = map_load(s, b);
+    else fv = skr::mdn_forced_load(s.forced, s.ld_forced, s.active ? s.nforced : nullptr, temps, b);
     // ---- stroke t-1: fold + draw (or the given x)
     if (s.active) {
         skr::fold_head_slabs(s.zs, s.ldz, s.nslab, s.slab, s.bias, s.nout, b, part, zrow);
-        if (w == 0) {
+        if constexpr (MAP) {
+            if (w == 0) map_sample(s, fv, zrow, x, xr, b);
+        } else if (w == 0) {
             const uint32_t key = skr::hash_key(*s.seed, 0x5A3Du, s.step);
+            const int row0 = s.row0 + (s.first_row != nullptr ? *s.first_row : 0);   // (a scalar load beside the seed's)
             const float tb = skr::mdn_temp_gather(fv, temps, s.temp);
             const skr::MdnDraw d =
-                skr::mdn_sample_wave(zrow, s.M, s.mode, tb, 1.f / tb, s.greedy, s.fix_pen, key, (uint32_t)(s.row0 + b), s.step);
+                skr::mdn_sample_wave(zrow, s.M, s.mode, tb, 1.f / tb, s.greedy, s.fix_pen, key, (uint32_t)(row0 + b), s.step);
             const skr::MdnForced fz = skr::mdn_forced_gather(fv);
             if (lane == 0) skr::mdn_emit_row(d, fz, s.step, s.mode, s.out_row + b * s.ld_out, x + b * 5, s.done + b, xr);
         }
@@ -131,7 +202,8 @@ __global__ __launch_bounds__(256) void decode_hyper_cell(const FwdArgs a, const 
 
 // a: the hyper cell's forward args (LayerNorm, H <= 256, one workgroup per
 // row: a.cluster <= 1; a.xp = the per-sketch z projection zp [B][ld_xp]),
-// s: the sampler of the previous stroke (s->active == 0: x [B][5] is read),
+// s: the sampler of the previous stroke (s->active == 0: x [B][5] is read;
+// s->job given: the slot-map sampler, above),
 // x [B][5] fp32 (in/out), w5 [5][ldw5] fp32 stroke rows of the hyper cell's
 // input weights (column offset applied by the caller, like a.xp).
 SKR_API int skr_decode_hyper_cell(const FwdArgs* a, const DecodeSample* s, float* x, const float* w5, int64_t ldw5,
@@ -144,13 +216,22 @@ SKR_API int skr_decode_hyper_cell(const FwdArgs* a, const DecodeSample* s, float
                       s->out_row == nullptr || s->seed == nullptr || (s->nforced != nullptr && s->forced == nullptr)))
         return -3;
     const dim3 grid(a->B), blk(256);
+    const bool map = s->job != nullptr;
+    if (map && (!s->active || s->pos == nullptr || s->first_row == nullptr || s->temps == nullptr ||
+                s->nforced != nullptr || s->nsteps < 1))
+        return -4;
+#define SKR_DECODE_CELL(NS)                                                                                   \
+    if (map) hipLaunchKernelGGL((decode_hyper_cell<NS, true>), grid, blk, 0, st, *a, *s, x, w5, ldw5);         \
+    else hipLaunchKernelGGL((decode_hyper_cell<NS, false>), grid, blk, 0, st, *a, *s, x, w5, ldw5);            \
+    break
     switch (a->R_nslab) {
-        case 1: hipLaunchKernelGGL(decode_hyper_cell<1>, grid, blk, 0, st, *a, *s, x, w5, ldw5); break;
-        case 2: hipLaunchKernelGGL(decode_hyper_cell<2>, grid, blk, 0, st, *a, *s, x, w5, ldw5); break;
-        case 4: hipLaunchKernelGGL(decode_hyper_cell<4>, grid, blk, 0, st, *a, *s, x, w5, ldw5); break;
-        case 8: hipLaunchKernelGGL(decode_hyper_cell<8>, grid, blk, 0, st, *a, *s, x, w5, ldw5); break;
-        default: hipLaunchKernelGGL(decode_hyper_cell<0>, grid, blk, 0, st, *a, *s, x, w5, ldw5); break;
+        case 1: SKR_DECODE_CELL(1);
+        case 2: SKR_DECODE_CELL(2);
+        case 4: SKR_DECODE_CELL(4);
+        case 8: SKR_DECODE_CELL(8);
+        default: SKR_DECODE_CELL(0);
     }
+#undef SKR_DECODE_CELL
     return SKR_CHECK_LAUNCH();
 }
 

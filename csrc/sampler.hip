@@ -33,12 +33,15 @@ __global__ __launch_bounds__(64) void mdn_sample_kernel(const float* __restrict_
                                                         int* __restrict__ done, float* __restrict__ params,
                                                         const float* __restrict__ forced, int64_t ld_forced,
                                                         const int* __restrict__ nforced,
-                                                        const float* __restrict__ temps) {
+                                                        const float* __restrict__ temps, int row0,
+                                                        const int* __restrict__ row_base) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const float fv = skr::mdn_forced_load(forced, ld_forced, nforced, temps, b);
     const uint32_t key = skr::hash_key(*seed, 0x5A3Du, step);
+    if (row_base != nullptr) row0 += *row_base;   // (a scalar load beside the seed's)
     const float tb = skr::mdn_temp_gather(fv, temps, temp);
-    const skr::MdnDraw d = skr::mdn_sample_wave(z + b * ldz, M, mode, tb, 1.f / tb, greedy, fix_pen, key, (uint32_t)b, step);
+    const skr::MdnDraw d =
+        skr::mdn_sample_wave(z + b * ldz, M, mode, tb, 1.f / tb, greedy, fix_pen, key, (uint32_t)(row0 + b), step);
     const skr::MdnForced f = skr::mdn_forced_gather(fv);
     if (lane != 0) return;
     skr::mdn_emit_row(d, f, step, mode, out_row + b * ld_out, next_x + b * ld_next, done + b);
@@ -65,7 +68,8 @@ __global__ __launch_bounds__(256) void mdn_sample_slabs_kernel(const float* __re
                                                                int* __restrict__ done,
                                                                const float* __restrict__ forced, int64_t ld_forced,
                                                                const int* __restrict__ nforced,
-                                                               const float* __restrict__ temps) {
+                                                               const float* __restrict__ temps,
+                                                               const int* __restrict__ row_base) {
     __shared__ float part[4][256];
     __shared__ float zrow[256];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -73,6 +77,7 @@ __global__ __launch_bounds__(256) void mdn_sample_slabs_kernel(const float* __re
     skr::fold_head_slabs(zs, ldz, nslab, slab, bias, nout, b, part, zrow);
     if (w != 0) return;
     const uint32_t key = skr::hash_key(*seed, 0x5A3Du, step);
+    if (row_base != nullptr) row0 += *row_base;   // (a scalar load beside the seed's)
     const float tb = skr::mdn_temp_gather(fv, temps, temp);
     const skr::MdnDraw d = skr::mdn_sample_wave(zrow, M, mode, tb, 1.f / tb, greedy, fix_pen, key, (uint32_t)(row0 + b), step);
     const skr::MdnForced f = skr::mdn_forced_gather(fv);
@@ -86,18 +91,30 @@ __global__ __launch_bounds__(256) void mdn_sample_slabs_kernel(const float* __re
 // with step < nforced[b] emit forced[b] instead of their draw (mdn_sample.h;
 // every row of forced is read when nforced is given). temps [B] (local rows
 // too): row b's temperature in place of temp; nullptr: temp for every row.
-SKR_API int skr_mdn_sample_slabs_temps(const float* zs, int64_t ldz, int nslab, int64_t slab, const float* bias, int B,
-                                       int M, int mode, float temp, int greedy, int fix_pen, const int64_t* seed,
-                                       uint32_t step, int row0, float* out_row, int64_t ld_out, float* next_x,
-                                       int64_t ld_next, int* done, const float* forced, int64_t ld_forced,
-                                       const int* nforced, const float* temps, hipStream_t s) {
+// row_base [1] (device memory, nullptr: 0): added to row0, so that a captured
+// launch serves any block of a longer job list (GraphDecoder.run(row0=)).
+SKR_API int skr_mdn_sample_slabs_rows(const float* zs, int64_t ldz, int nslab, int64_t slab, const float* bias, int B,
+                                      int M, int mode, float temp, int greedy, int fix_pen, const int64_t* seed,
+                                      uint32_t step, int row0, float* out_row, int64_t ld_out, float* next_x,
+                                      int64_t ld_next, int* done, const float* forced, int64_t ld_forced,
+                                      const int* nforced, const float* temps, const int* row_base, hipStream_t s) {
     if (M < 1 || M > 32 || nslab < 1) return -2;
     if (nforced != nullptr && forced == nullptr) return -2;
     if (B <= 0) return 0;
     hipLaunchKernelGGL(mdn_sample_slabs_kernel, dim3(B), dim3(256), 0, s, zs, ldz, nslab, slab, bias, 3 + 6 * M, M,
                        mode, temp, greedy, fix_pen, seed, step, row0, out_row, ld_out, next_x, ld_next, done, forced,
-                       ld_forced, nforced, temps);
+                       ld_forced, nforced, temps, row_base);
     return SKR_CHECK_LAUNCH();
+}
+
+SKR_API int skr_mdn_sample_slabs_temps(const float* zs, int64_t ldz, int nslab, int64_t slab, const float* bias, int B,
+                                       int M, int mode, float temp, int greedy, int fix_pen, const int64_t* seed,
+                                       uint32_t step, int row0, float* out_row, int64_t ld_out, float* next_x,
+                                       int64_t ld_next, int* done, const float* forced, int64_t ld_forced,
+                                       const int* nforced, const float* temps, hipStream_t s) {
+    return skr_mdn_sample_slabs_rows(zs, ldz, nslab, slab, bias, B, M, mode, temp, greedy, fix_pen, seed, step, row0,
+                                     out_row, ld_out, next_x, ld_next, done, forced, ld_forced, nforced, temps, nullptr,
+                                     s);
 }
 
 SKR_API int skr_mdn_sample_slabs_forced(const float* zs, int64_t ldz, int nslab, int64_t slab, const float* bias, int B,
@@ -117,16 +134,29 @@ SKR_API int skr_mdn_sample_slabs(const float* zs, int64_t ldz, int nslab, int64_
                                        out_row, ld_out, next_x, ld_next, done, nullptr, 0, nullptr, s);
 }
 
-SKR_API int skr_mdn_sample_temps(const float* z, int64_t ldz, int B, int M, int mode, float temp, int greedy,
-                                 int fix_pen, const int64_t* seed, uint32_t step, float* out_row, int64_t ld_out,
-                                 float* next_x, int64_t ld_next, int* done, float* params, const float* forced,
-                                 int64_t ld_forced, const int* nforced, const float* temps, hipStream_t s) {
+// row0 + *row_base (nullptr: 0): the hash row of local row 0 (a block of a
+// larger job list keeps its rows' noise; done, nforced and temps stay indexed
+// by the local row).
+SKR_API int skr_mdn_sample_rows(const float* z, int64_t ldz, int B, int M, int mode, float temp, int greedy,
+                                int fix_pen, const int64_t* seed, uint32_t step, int row0, float* out_row,
+                                int64_t ld_out, float* next_x, int64_t ld_next, int* done, float* params,
+                                const float* forced, int64_t ld_forced, const int* nforced, const float* temps,
+                                const int* row_base, hipStream_t s) {
     if (M < 1 || M > 32) return -2;
     if (nforced != nullptr && forced == nullptr) return -2;
     if (B <= 0) return 0;
     hipLaunchKernelGGL(mdn_sample_kernel, dim3(B), dim3(64), 0, s, z, ldz, M, mode, temp, greedy, fix_pen, seed, step,
-                       out_row, ld_out, next_x, ld_next, done, params, forced, ld_forced, nforced, temps);
+                       out_row, ld_out, next_x, ld_next, done, params, forced, ld_forced, nforced, temps, row0,
+                       row_base);
     return SKR_CHECK_LAUNCH();
+}
+
+SKR_API int skr_mdn_sample_temps(const float* z, int64_t ldz, int B, int M, int mode, float temp, int greedy,
+                                 int fix_pen, const int64_t* seed, uint32_t step, float* out_row, int64_t ld_out,
+                                 float* next_x, int64_t ld_next, int* done, float* params, const float* forced,
+                                 int64_t ld_forced, const int* nforced, const float* temps, hipStream_t s) {
+    return skr_mdn_sample_rows(z, ldz, B, M, mode, temp, greedy, fix_pen, seed, step, 0, out_row, ld_out, next_x,
+                               ld_next, done, params, forced, ld_forced, nforced, temps, nullptr, s);
 }
 
 SKR_API int skr_mdn_sample_forced(const float* z, int64_t ldz, int B, int M, int mode, float temp, int greedy,

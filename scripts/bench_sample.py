@@ -18,6 +18,16 @@ line with
   (row-steps the decoder computed, padding rows included);
 * ``steps_run`` -- decode steps per sketch batch after the early exit.
 
+``--impl stream --jobs J [--slots S] [--chunk C]`` times bulk generation
+(``sample.stream.StreamDecoder``: S decoder rows, finished rows refilled with
+the next of J latents) and reports the same fields plus ``occupancy`` (valid
+strokes per computed row-step). With ``--jobs J`` the ``graph`` arm loops
+``GraphDecoder.run`` over the same J latents in batches of ``--batch``, so the
+two arms deliver the same number of sketches. ``--impl`` takes a
+comma-separated list (``graph,stream,graph,stream``): the arms run in that
+order in one process on one model, one JSON line each; ``--chunk`` takes a
+list too, every stream arm running once per value.
+
 ``--train-steps N`` first trains the model N steps on synthetic sketches
 (random-init models end their sketches after a handful of strokes, which
 makes every throughput look like padding).
@@ -54,9 +64,15 @@ def main():
     ap.add_argument("--train-steps", type=int, default=0, help="train this many steps first (synthetic data)")
     ap.add_argument("--no-early-exit", action="store_true")
     ap.add_argument("--fp8", action="store_true", help="MX-fp8 h W_h in the HyperLSTM step decoder (BASELINE config 5)")
-    ap.add_argument("--impl", default="graph", choices=["graph", "fused"],
+    ap.add_argument("--impl", default="graph",
                     help="graph: GraphDecoder; fused: the whole-sketch kernel (fused_vae_decoder: plain lstm and "
-                         "layer_norm decoders)")
+                         "layer_norm decoders); stream: StreamDecoder over --jobs latents; a comma-separated list "
+                         "runs its arms in order in one process")
+    ap.add_argument("--jobs", type=int, default=0,
+                    help="latents to decode per repetition (stream; graph: looped in batches of --batch)")
+    ap.add_argument("--slots", type=int, default=0, help="stream: decoder rows (default --batch)")
+    ap.add_argument("--chunk", default=None,
+                    help="stream: decode steps per replayed graph (comma-separated: one run per value)")
     ap.add_argument("--prefix_len", type=int, default=0,
                     help="feed a synthetic prefix of this many strokes to every row (sketch completion)")
     ap.add_argument("--temperatures", default=None,
@@ -64,6 +80,15 @@ def main():
     a = ap.parse_args()
     if not 0 <= a.prefix_len <= a.steps:
         ap.error("--prefix_len must lie in [0, --steps]")
+    arms = a.impl.split(",")
+    if not all(x in ("graph", "fused", "stream") for x in arms):
+        ap.error("--impl: graph, fused, stream, or a comma-separated list of them")
+    if "stream" in arms and (a.jobs < 1 or a.prefix_len or a.fp8):
+        ap.error("--impl stream needs --jobs >= 1 and takes neither --prefix_len nor --fp8")
+    if len(arms) > 1 or a.jobs > 0:
+        if "fused" in arms or a.prefix_len or a.temperatures:
+            ap.error("--jobs and lists of arms take graph and stream, without --prefix_len and --temperatures")
+    chunks = [int(c) for c in a.chunk.split(",")] if a.chunk else [None]
     import numpy as np
     import torch
     from sketch_rnn_amd import ops
@@ -101,6 +126,8 @@ def main():
     if a.temperatures is not None:
         tv = torch.tensor([float(t) for t in a.temperatures.split(",")], device="cuda")
         pre["temperature"] = tv[torch.arange(a.batch, device="cuda") % tv.numel()]
+    if len(arms) > 1 or a.jobs > 0:
+        return bulk_arms(a, arms, chunks, model, train_cost)
     dec, impl = None, a.impl
     if a.impl == "fused":
         from sketch_rnn_amd.sample.fused import NotCoResident, fused_vae_decoder
@@ -142,6 +169,60 @@ def main():
                       "host_loop_strokes_per_s": round(host_sps, 1),
                       "speedup_valid_vs_host": round(valid_sps / host_sps, 1),
                       "mean_len": total_len / a.batch / a.reps}), flush=True)
+
+
+def bulk_arms(a, arms, chunks, model, train_cost):
+    """The arms of a job list, in order, on one model: ``graph`` loops
+    GraphDecoder.run over the latents in batches of --batch, ``stream`` hands
+    them to one StreamDecoder of --slots rows. One JSON line per run."""
+    import torch
+    from sketch_rnn_amd.sample.sampler import GraphDecoder
+    from sketch_rnn_amd.sample.stream import StreamDecoder
+    J = a.jobs if a.jobs > 0 else a.batch
+    slots = a.slots or a.batch
+    z = torch.randn(J, model.cfg.z_size, device="cuda", generator=torch.Generator(device="cuda").manual_seed(0))
+    decs = {}
+    for arm in arms:
+        for chunk in (chunks if arm == "stream" else [None]):
+            key = (arm, chunk)
+            if key not in decs:
+                if arm == "stream":
+                    decs[key] = StreamDecoder(model, slots, a.steps, a.temperature, chunk=chunk)
+                    decs[key].run(z, seed=0)          # capture
+                else:
+                    decs[key] = GraphDecoder(model, a.batch, a.steps, a.temperature, early_exit=not a.no_early_exit)
+                    decs[key].run(seed=0, z=z[:a.batch])
+            dec = decs[key]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            total_len = total_pos = steps = 0
+            for r in range(a.reps):
+                if arm == "stream":
+                    _, lens = dec.run(z, seed=r + 1)
+                    total_len += int(lens.sum())
+                    total_pos += dec.slot_steps
+                    steps += dec.steps_run
+                else:
+                    for j0 in range(0, J - a.batch + 1, a.batch):
+                        _, lens = dec.run(seed=r + 1, z=z[j0:j0 + a.batch])
+                        total_len += int(lens.sum())
+                        total_pos += a.batch * dec.steps_run
+                        steps += dec.steps_run
+            torch.cuda.synchronize()
+            wall = time.perf_counter() - t0
+            done = J if arm == "stream" else J // a.batch * a.batch
+            print(json.dumps({"metric": "sampled valid strokes/sec (temperature %.2f)" % a.temperature,
+                              "config": a.config, "impl": arm, "path": getattr(dec, "impl", "graph"),
+                              "dtype": a.dtype, "jobs": done, "batch": a.batch if arm == "graph" else slots,
+                              "chunk": getattr(dec, "chunk", None) if arm == "stream" else None,
+                              "steps": a.steps, "train_steps": a.train_steps, "train_cost": train_cost,
+                              "valid_strokes_per_s": round(total_len / wall, 1),
+                              "decode_positions_per_s": round(total_pos / wall, 1),
+                              "steps_run": steps / a.reps,
+                              "occupancy": round(total_len / total_pos, 4) if total_pos else 0.0,
+                              "ms_per_job_list": round(1000 * wall / a.reps, 3),
+                              "ms_per_decode_step": round(1000 * wall / max(steps, 1), 4),
+                              "mean_len": total_len / done / a.reps}), flush=True)
 
 
 if __name__ == "__main__":

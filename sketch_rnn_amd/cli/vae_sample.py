@@ -23,6 +23,18 @@ temperature, all in one batch with a temperature per row, and lays the grid
 out with one line per latent and the temperatures as its columns (after the
 original in ``reconstruct``).
 
+``--mode bulk --n J --slots S [--chunk C] --out_pack FILE`` generates J
+sketches from latents drawn as in ``random`` and writes them as a sketch
+pack (``data.quickdraw.save_pack``, split ``train``, stroke-3 in model units
+cut at each decoded length) instead of a grid. It decodes through
+``sample.stream.StreamDecoder``: S decoder rows, a finished row taking the
+next latent instead of padding until the longest sketch of its batch ends
+(on a GPU with the four-launch HyperLSTM stroke; blocks of S through the
+graph decoder elsewhere; the recycling path is bf16, so on a GPU bulk mode
+computes in bf16 unless ``--dtype fp32`` is given). Super-batches of at most 16384 sketches bound the
+memory. Prints one JSON line: ``steps_run``, ``slot_steps``,
+``valid_strokes``, ``occupancy`` (valid strokes per computed row-step).
+
 Writes a stroke-3 SVG grid. ``--png PATH`` writes the same grid (the same
 sketches, order and columns) as a PNG of ``--png_size`` pixels per sketch,
 rasterised on the model's device by ``ops.raster.rasterize``. ``--mode
@@ -49,6 +61,9 @@ import sys
 import numpy as np
 
 
+BULK_SUPER = 16384     # --mode bulk: jobs per StreamDecoder.run (the per-job constants are held for a whole run)
+
+
 def slerp(p0, p1, t):
     p0, p1 = np.asarray(p0, np.float64), np.asarray(p1, np.float64)
     omega = np.arccos(np.clip(np.dot(p0 / np.linalg.norm(p0), p1 / np.linalg.norm(p1)), -1, 1))
@@ -58,11 +73,36 @@ def slerp(p0, p1, t):
     return np.sin((1.0 - t) * omega) / so * p0 + np.sin(t * omega) / so * p1
 
 
+def _bulk(a, model, cfg, zs, labels, device, dtype) -> int:
+    """``--mode bulk``: the latents through StreamDecoder in super-batches, the pack, the JSON line."""
+    import json
+    import torch
+    from ..data.quickdraw import save_pack
+    from ..data.strokes import to_normal_strokes
+    from ..sample.stream import StreamDecoder
+    dec = StreamDecoder(model, a.slots, cfg.max_seq_len, a.temperature, a.greedy, chunk=a.chunk)
+    total = {"steps_run": 0, "slot_steps": 0, "valid_strokes": 0}
+    sketches = []
+    for j0 in range(0, a.n, BULK_SUPER):
+        zt = torch.as_tensor(zs[j0:j0 + BULK_SUPER], dtype=torch.float32, device=device)
+        s, lens = dec.run(zt, labels=torch.as_tensor(labels[j0:j0 + BULK_SUPER], device=device), seed=a.seed,
+                          first_row=j0)
+        s, lens = s.cpu().numpy(), lens.cpu().numpy()
+        sketches.extend(to_normal_strokes(x[:n]) for x, n in zip(s, lens))
+        for k in total:
+            total[k] += getattr(dec, k)
+    save_pack(a.out_pack, {"train": (sketches, labels)})
+    total["occupancy"] = total["valid_strokes"] / total["slot_steps"] if total["slot_steps"] else 0.0
+    print(json.dumps(dict(mode="bulk", impl=dec.impl, dtype=dtype, n=a.n, slots=a.slots, chunk=dec.chunk, **total)))
+    return 0
+
+
 def main(argv=None) -> int:
     p = argparse.ArgumentParser()
     p.add_argument("--save_dir", default="save/vae")
     p.add_argument("--out", default="vae_samples.svg")
-    p.add_argument("--mode", choices=["random", "class", "interpolate", "reconstruct", "complete"], default="random")
+    p.add_argument("--mode", choices=["random", "class", "interpolate", "reconstruct", "complete", "bulk"],
+                   default="random")
     p.add_argument("--n", type=int, default=10)
     p.add_argument("--label", type=int, default=0)
     p.add_argument("--temperature", type=float, default=0.5)
@@ -104,7 +144,20 @@ def main(argv=None) -> int:
                    help="reconstruct: rasterise each original in its fitted frame and its reconstructions in the "
                         "same frame, print the mean soft IoU per decoded column and write the per-sketch values "
                         "to <out>.iou.json")
+    p.add_argument("--slots", type=int, default=128, help="bulk: decoder rows kept busy")
+    p.add_argument("--chunk", type=int, default=None, help="bulk: decode steps between two refills of finished rows")
+    p.add_argument("--out_pack", default=None, metavar="FILE", help="bulk: the sketch pack (.npz) to write")
+    p.add_argument("--dtype", choices=["fp32", "bf16"], default=None,
+                   help="bulk: compute dtype of the decode (default bf16 on a GPU, where the recycling path of "
+                        "StreamDecoder needs it; fp32 elsewhere)")
     a = p.parse_args(argv)
+    if a.mode == "bulk":
+        if not a.out_pack:
+            p.error("--mode bulk needs --out_pack")
+        if a.n < 0 or a.slots < 1 or (a.chunk is not None and a.chunk < 1):
+            p.error("--mode bulk needs --n >= 0, --slots >= 1 and --chunk >= 1")
+        if a.temperatures is not None or a.fused or a.fp8 or a.png or a.raster_iou:
+            p.error("--mode bulk takes none of --temperatures, --fused, --fp8, --png, --raster_iou")
     if a.fused and not a.device_sampler:
         p.error("--fused needs --device_sampler")
     if a.raster_iou and a.mode != "reconstruct":
@@ -146,6 +199,15 @@ def main(argv=None) -> int:
         zs = np.stack([slerp(z0, z1, t) for t in np.linspace(0, 1, a.n)])
     labels = np.full(a.n, a.label if a.mode == "class" else 0)
     N = cfg.max_seq_len
+    if a.mode == "bulk":
+        from .. import ops
+        # the recycling path is the bf16 four-launch stroke: a GPU run takes bf16 unless told otherwise
+        dtype, saved = a.dtype or ("bf16" if device.startswith("cuda") else "fp32"), ops.get_compute_dtype()
+        ops.set_compute_dtype(dtype)
+        try:
+            return _bulk(a, model, cfg, zs, labels, device, dtype)
+        finally:
+            ops.set_compute_dtype(saved)
     prefix = plen = shown = None      # complete: [rows, P, 5] stroke-5 prefixes and their lengths; shown: data sketches
     group = 1                         # decoded sketches per shown one
     if from_data:

@@ -49,8 +49,10 @@ def _mix32(x: torch.Tensor) -> torch.Tensor:
     return x
 
 
-def hash_uniform(seed, stream: int, step: int, shape, device=None) -> torch.Tensor:
+def hash_uniform(seed, stream: int, step: int, shape, device=None, offset: int = 0) -> torch.Tensor:
     """U[0,1) per element of ``shape`` from (seed, stream, step, flat index).
+    ``offset`` is added to the flat index (elements ``offset ..`` of a longer
+    array, without forming the ones before them).
 
     ``seed`` may be a Python int or a 1-element int64 tensor (device-resident
     seeds keep the HIP-graph-captured step valid across replays)."""
@@ -65,6 +67,8 @@ def hash_uniform(seed, stream: int, step: int, shape, device=None) -> torch.Tens
         s64 = torch.tensor(int(seed) & _M32, dtype=torch.int64, device=device)
     key = _mix32((s64 * 0x9E3779B1 + base) & _M32)
     idx = torch.arange(n, dtype=torch.int64, device=device)
+    if offset:
+        idx = (idx + int(offset)) & _M32
     h = _mix32(idx ^ key)
     h = _mix32(h + key)
     return ((h >> 8).to(torch.float32) * (1.0 / 16777216.0)).view(*shape)

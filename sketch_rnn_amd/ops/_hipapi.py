@@ -385,6 +385,22 @@ class DecodeSample(C.Structure):
         ("done", _p),
         ("forced", _p), ("ld_forced", _i64), ("nforced", _p),
         ("temps", _p),
+        ("job", _p), ("pos", _p), ("first_row", _p), ("nsteps", _i),     # slot map (sample/stream.py)
+    ]
+
+
+class RefillArgs(C.Structure):
+    """Mirror of ``RefillArgs`` in csrc/decode_refill.hip (slot refill of the
+    recycling bulk decoder, sample/stream.py)."""
+    _fields_ = [
+        ("slots", _i), ("chunk", _i), ("poison", _i),
+        ("ctl", _p), ("done", _p), ("job", _p), ("pos", _p), ("assign", _p),
+        ("A", _p), ("jA", _p), ("a_bytes", _i),
+        ("CC", _p), ("jCC", _p), ("cc_bytes", _i),
+        ("HCC", _p), ("jHCC", _p), ("hcc_bytes", _i),
+        ("ZP", _p), ("jZP", _p), ("zp_bytes", _i),
+        ("temps", _p), ("jtemps", _p),
+        ("X", _p),
     ]
 
 
@@ -437,9 +453,15 @@ class HipLib:
         lib.skr_mdn_sample_temps.argtypes = [_p, _i64, _i, _i, _i, _f, _i, _i, _p, _u32, _p, _i64, _p, _i64, _p, _p,
                                              _p, _i64, _p, _p, _p]
         lib.skr_mdn_sample_temps.restype = _i
+        lib.skr_mdn_sample_rows.argtypes = [_p, _i64, _i, _i, _i, _f, _i, _i, _p, _u32, _i, _p, _i64, _p, _i64, _p, _p,
+                                            _p, _i64, _p, _p, _p, _p]
+        lib.skr_mdn_sample_rows.restype = _i
         lib.skr_mdn_sample_slabs_temps.argtypes = [_p, _i64, _i, _i64, _p, _i, _i, _i, _f, _i, _i, _p, _u32, _i, _p,
                                                    _i64, _p, _i64, _p, _p, _i64, _p, _p, _p]
         lib.skr_mdn_sample_slabs_temps.restype = _i
+        lib.skr_mdn_sample_slabs_rows.argtypes = [_p, _i64, _i, _i64, _p, _i, _i, _i, _f, _i, _i, _p, _u32, _i, _p,
+                                                  _i64, _p, _i64, _p, _p, _i64, _p, _p, _p, _p]
+        lib.skr_mdn_sample_slabs_rows.restype = _i
         lib.skr_inproj_fwd.argtypes = [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]
         lib.skr_inproj_fwd.restype = _i
         lib.skr_inproj_bwd.argtypes = [_p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p]
@@ -550,6 +572,8 @@ class HipLib:
         lib.skr_hash_normal.restype = _i
         lib.skr_decode_hyper_cell.argtypes = [C.POINTER(LstmFwdArgs), C.POINTER(DecodeSample), _p, _p, _i64, _p]
         lib.skr_decode_hyper_cell.restype = _i
+        lib.skr_decode_refill.argtypes = [C.POINTER(RefillArgs), _p]
+        lib.skr_decode_refill.restype = _i
         lib.skr_decode_ref.argtypes = [C.POINTER(DecArgs), _p]
         lib.skr_decode_ref.restype = _i
         lib.skr_decode_vae.argtypes = [C.POINTER(DecVaeArgs), _p]
@@ -574,6 +598,7 @@ class HipLib:
                           ("skr_decode_vae_ln_args_size", DecVaeLnArgs),
                           ("skr_gemm_problem_size", GemmProblem),
                           ("skr_decode_sample_size", DecodeSample),
+                          ("skr_decode_refill_size", RefillArgs),
                           ("skr_chain_sync_size", ChainSync),
                           ("skr_colsum_job_size", CsJob),
                           ("skr_small_gemm_prob_size", SgProb)):

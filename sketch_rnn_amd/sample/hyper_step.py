@@ -77,12 +77,24 @@ def hyper_step_ok(model, B: int) -> bool:
     return H % 64 == 0 and Hh % 64 == 0 and cfg.num_mixture <= 32
 
 
+def fused_shape_ok(H: int, Hh: int, E: int) -> bool:
+    """Shape limits of the four-launch stroke (csrc/hyper_mod.hip in decode
+    mode): hyper width 256, embedding <= 32, 32-unit tiles."""
+    return FUSED and Hh == 256 and E <= 32 and H % 32 == 0
+
+
+def fused_ok(model, B: int) -> bool:
+    """A :class:`HyperStepDecoder` of B rows takes ``step_fused``."""
+    cfg = model.cfg
+    return hyper_step_ok(model, B) and fused_shape_ok(cfg.dec_rnn_size, cfg.hyper_num_units, model.dec.embed)
+
+
 def wide_ok(model) -> bool:
     """One decoder over up to 1024 rows (128-row blocks inside each launch)
     instead of 128-row chunks on concurrent streams: the four-launch stroke's
     shape limits (:class:`HyperStepDecoder` ``fused``)."""
     cfg = model.cfg
-    return WIDE and cfg.hyper_num_units == 256 and cfg.hyper_embedding_size <= 32 and cfg.dec_rnn_size % 32 == 0
+    return WIDE and fused_shape_ok(cfg.dec_rnn_size, cfg.hyper_num_units, cfg.hyper_embedding_size)
 
 
 WIDE = True   # one decoder over B > 128 rows (False: tests of the 128-row chunked decoders)
@@ -116,7 +128,7 @@ class HyperStepDecoder:
         assert min(self.S_m, self.S_y, self.S_o) >= 1
         # four-launch stroke (step_fused): hyper_mod's shape limits (Hh == 256,
         # E <= 32, 32-unit tiles, <= 4 main-GEMM slabs)
-        self.fused = FUSED and Hh == 256 and self.E <= 32 and H % 32 == 0
+        self.fused = fused_shape_ok(H, Hh, self.E)
         self.fp8 = bool(fp8) and self.fused and H % 512 == 0 and H <= 2048 and G % 128 == 0
         if self.fused:
             self.S_m = 4 if self.S_m >= 4 else 2 if self.S_m >= 2 else 1
@@ -321,7 +333,9 @@ class HyperStepDecoder:
         ``forced [B, 5]`` fp32 (any row stride) with ``nforced [B]`` int32: rows
         with ``step < nforced[b]`` take ``forced[b]`` as their stroke instead of
         the draw (``csrc/mdn_sample.h``). ``temps [B]`` fp32: row b samples at
-        ``temps[b]`` instead of ``temp``."""
+        ``temps[b]`` instead of ``temp``. A caller may set the result's
+        ``first_row`` to an int32 device word that is added to ``row0`` (a
+        captured launch then serves any block of a job list)."""
         s = DecodeSample()
         s.active = 1
         s.zs, s.ldz, s.nslab, s.slab = self.ZS.data_ptr(), 128, self.S_o, self.B * 128

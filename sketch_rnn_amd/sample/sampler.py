@@ -22,6 +22,8 @@ decoders step through :class:`~.hyper_step.HyperStepDecoder` (state in
 place, seven hand-written kernels per stroke); the reference model and
 the VAE's plain ``lstm`` and ``layer_norm`` decoders have whole-sketch
 decoders in :mod:`.fused` (the VAE ones are opt-in: ``vae_sample --fused``).
+Many sketches at once go through :mod:`.stream`, which refills finished rows
+with the next latent instead of padding them (``vae_sample --mode bulk``).
 """
 from __future__ import annotations
 
@@ -217,7 +219,7 @@ def check_temperature(name: str, temperature, B: int, dev) -> torch.Tensor:
 def mdn_sample_torch(zh: torch.Tensor, M_: int, mode: int, temp, greedy: bool, fix_pen: bool,
                      seed, step: int, out_row: torch.Tensor, next_x: torch.Tensor, done: torch.Tensor,
                      params: Optional[torch.Tensor] = None, forced: Optional[torch.Tensor] = None,
-                     nforced: Optional[torch.Tensor] = None) -> None:
+                     nforced: Optional[torch.Tensor] = None, row0: int = 0) -> None:
     """PyTorch transcription of ``csrc/sampler.hip`` (same hash random
     numbers, same draws): the CPU path of :class:`GraphDecoder` and the
     oracle the kernel is tested against.
@@ -231,11 +233,14 @@ def mdn_sample_torch(zh: torch.Tensor, M_: int, mode: int, temp, greedy: bool, f
     ``temp`` is a float, or an fp32 ``[B]`` tensor of per-row temperatures:
     row b then uses ``temp[b]`` wherever the scalar is used, with the
     reciprocal taken in fp32 per row as the kernel takes it (the scalar form
-    keeps its Python-float reciprocal)."""
+    keeps its Python-float reciprocal).
+
+    ``row0``: the hash row of local row 0 (row b draws the noise of row
+    ``row0 + b``; everything else stays indexed by the local row)."""
     from ..models.cells import hash_uniform
     B = zh.shape[0]
     z = zh.float()
-    u = hash_uniform(seed, _SAMPLE_STREAM, step, (B, 4), device=z.device)
+    u = hash_uniform(seed, _SAMPLE_STREAM, step, (B, 4), device=z.device, offset=4 * int(row0))
     use_t = mode == 1 or step > 1
     if torch.is_tensor(temp):      # per row: 1 / temps and temps broadcast over the row's columns, in fp32
         tv = temp.to(z.device, torch.float32).reshape(B)
@@ -291,61 +296,45 @@ def mdn_sample_torch(zh: torch.Tensor, M_: int, mode: int, temp, greedy: bool, f
 def mdn_sample_device(zh: torch.Tensor, M_: int, mode: int, temp, greedy: bool, fix_pen: bool,
                       seed: torch.Tensor, step: int, out_row: torch.Tensor, next_x: torch.Tensor,
                       done: torch.Tensor, params: Optional[torch.Tensor] = None,
-                      forced: Optional[torch.Tensor] = None, nforced: Optional[torch.Tensor] = None) -> None:
+                      forced: Optional[torch.Tensor] = None, nforced: Optional[torch.Tensor] = None,
+                      row0: int = 0, row_base: Optional[torch.Tensor] = None) -> None:
     """``csrc/sampler.hip`` on a GPU tensor, :func:`mdn_sample_torch` elsewhere.
     ``forced [B, 5]`` (any row stride) with ``nforced [B]`` int32: rows with
     ``step < nforced[b]`` emit ``forced[b]`` instead of their draw. ``temp``: a
-    float, or an fp32 ``[B]`` tensor of per-row temperatures."""
+    float, or an fp32 ``[B]`` tensor of per-row temperatures. The hash row of
+    local row 0 is ``row0`` plus the int32 device word ``row_base`` (a captured
+    launch then serves any block of a longer job list)."""
     if torch.is_tensor(temp) and (temp.dtype != torch.float32 or temp.shape != (zh.shape[0],)):
         raise ValueError("mdn_sample_device: per-row temperatures must be an fp32 [B] tensor")
     if (forced is None) != (nforced is None):
         raise ValueError("mdn_sample_device: forced and nforced go together")
     if zh.device.type != "cuda":
         return mdn_sample_torch(zh, M_, mode, temp, greedy, fix_pen, seed, step, out_row, next_x, done, params,
-                                forced, nforced)
+                                forced, nforced, row0 + (int(row_base) if row_base is not None else 0))
     assert zh.dtype == torch.float32 and zh.stride(1) == 1 and zh.shape[1] >= 3 + 6 * M_
     assert out_row.dtype == torch.float32 and out_row.stride(-1) == 1 and out_row.shape[0] == zh.shape[0]
     assert next_x.shape == (zh.shape[0], 5) and next_x.stride(-1) == 1
     assert done.dtype == torch.int32 and done.numel() == zh.shape[0] and seed.dtype == torch.int64
     from ..utils import native
     lib = native.require_hip()
-    import ctypes
     B = zh.shape[0]
     if nforced is not None:
         assert forced.dtype == torch.float32 and forced.shape == (B, 5) and forced.stride(1) == 1
         assert nforced.dtype == torch.int32 and nforced.shape == (B,) and nforced.stride(0) == 1
-    if torch.is_tensor(temp):
-        temps = temp.contiguous()      # the kernel indexes temps[b]; a strided view is copied
-        assert temps.device == zh.device
-        rc = lib.lib.skr_mdn_sample_temps(
-            zh.data_ptr(), zh.stride(0), B, M_, mode, 1.0, int(greedy), int(fix_pen), seed.data_ptr(), step,
-            out_row.data_ptr(), out_row.stride(0), next_x.data_ptr(), next_x.stride(0), done.data_ptr(),
-            params.data_ptr() if params is not None else None,
-            forced.data_ptr() if nforced is not None else None, forced.stride(0) if nforced is not None else 0,
-            nforced.data_ptr() if nforced is not None else None, temps.data_ptr(),
-            torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise RuntimeError("skr_mdn_sample_temps failed (%d)" % rc)
-        return
-    if nforced is not None:
-        rc = lib.lib.skr_mdn_sample_forced(
-            zh.data_ptr(), zh.stride(0), B, M_, mode, temp, int(greedy), int(fix_pen), seed.data_ptr(), step,
-            out_row.data_ptr(), out_row.stride(0), next_x.data_ptr(), next_x.stride(0), done.data_ptr(),
-            params.data_ptr() if params is not None else None, forced.data_ptr(), forced.stride(0),
-            nforced.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise RuntimeError("skr_mdn_sample_forced failed (%d)" % rc)
-        return
-    rc = lib.lib.skr_mdn_sample(ctypes.c_void_p(zh.data_ptr()), ctypes.c_int64(zh.stride(0)), ctypes.c_int(zh.shape[0]),
-                                ctypes.c_int(M_), ctypes.c_int(mode), ctypes.c_float(temp), ctypes.c_int(int(greedy)),
-                                ctypes.c_int(int(fix_pen)), ctypes.c_void_p(seed.data_ptr()), ctypes.c_uint32(step),
-                                ctypes.c_void_p(out_row.data_ptr()), ctypes.c_int64(out_row.stride(0)),
-                                ctypes.c_void_p(next_x.data_ptr()), ctypes.c_int64(next_x.stride(0)),
-                                ctypes.c_void_p(done.data_ptr()),
-                                ctypes.c_void_p(params.data_ptr() if params is not None else 0),
-                                ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    # one entry point for every combination (the others forward to it); a strided temperature view is copied,
+    # the kernel indexes temps[b]
+    temps = temp.contiguous() if torch.is_tensor(temp) else None
+    assert temps is None or temps.device == zh.device
+    assert row_base is None or (row_base.dtype == torch.int32 and row_base.numel() == 1 and row_base.is_cuda)
+    rc = lib.lib.skr_mdn_sample_rows(
+        zh.data_ptr(), zh.stride(0), B, M_, mode, 1.0 if temps is not None else temp, int(greedy), int(fix_pen),
+        seed.data_ptr(), step, int(row0), out_row.data_ptr(), out_row.stride(0), next_x.data_ptr(),
+        next_x.stride(0), done.data_ptr(), params.data_ptr() if params is not None else None,
+        forced.data_ptr() if nforced is not None else None, forced.stride(0) if nforced is not None else 0,
+        nforced.data_ptr() if nforced is not None else None, temps.data_ptr() if temps is not None else None,
+        row_base.data_ptr() if row_base is not None else None, torch.cuda.current_stream().cuda_stream)
     if rc != 0:
-        raise RuntimeError("skr_mdn_sample failed (%d)" % rc)
+        raise RuntimeError("skr_mdn_sample_rows failed (%d)" % rc)
 
 
 class GraphDecoder:
@@ -404,6 +393,8 @@ class GraphDecoder:
         self.early_exit = bool(early_exit)
         self.fp8 = bool(fp8)   # MX-fp8 h W_h in the HyperLSTM step decoders (BASELINE config 5)
         self.steps_run = 0
+        # hash row of row 0 (run(row0=)): a device word every sampler call reads, so it never causes a recapture
+        self.row_base = torch.zeros(1, dtype=torch.int32, device=dev)
         self._carry = {}     # tensors handed from one chunk to the next (state, next input, zc)
 
     _MAX_CHUNKS = 8          # concurrent 128-row step decoders (one HIP stream each)
@@ -468,18 +459,21 @@ class GraphDecoder:
                             t - 1, r0, self.out[r0:r0 + n, t - 1], done, self.seed, self.Mx, self.mode, self.temp,
                             self.greedy, self.fix_pen, forced=self.prefix[r0:r0 + n, t - 1],
                             nforced=self.nforced[r0:r0 + n], temps=self.temps[r0:r0 + n])
+                        if smp is not None:
+                            smp.first_row = self.row_base.data_ptr()     # run(row0=): a device word
                         st.step_fused(t, smp)
                     if t1 == N:
                         st.head()          # the last stroke: head + sampler
-                        rc = lib.skr_mdn_sample_slabs_temps(
+                        rc = lib.skr_mdn_sample_slabs_rows(
                             st.ZS.data_ptr(), 128, st.S_o, n * 128, st._w["bo"].data_ptr(), n, self.Mx, self.mode,
-                            self.temp, int(self.greedy), int(self.fix_pen), self.seed.data_ptr(), N - 1, r0,
+                            self.temp, int(self.greedy), int(self.fix_pen), self.seed.data_ptr(), N - 1,
+                            r0,
                             self.out[r0, N - 1].data_ptr(), ld_out, st.X.data_ptr(), 5, done.data_ptr(),
                             self.prefix[r0, N - 1].data_ptr(), ld_pre, self.nforced[r0:].data_ptr(),
-                            self.temps[r0:].data_ptr(),
+                            self.temps[r0:].data_ptr(), self.row_base.data_ptr(),
                             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
                         if rc != 0:
-                            raise RuntimeError("skr_mdn_sample_slabs_temps failed (%d)" % rc)
+                            raise RuntimeError("skr_mdn_sample_slabs_rows failed (%d)" % rc)
                 continue
             with torch.cuda.stream(stream):
                 if t0 == 0:
@@ -490,15 +484,15 @@ class GraphDecoder:
                     nx = torch.empty(n, 5, device=self.dev)
 
                     def sample(zs, ldz, nslab, slab, bias, r0=r0, n=n, t=t, nx=nx):
-                        rc = lib.skr_mdn_sample_slabs_temps(
+                        rc = lib.skr_mdn_sample_slabs_rows(
                             zs.data_ptr(), ldz, nslab, slab, bias.data_ptr(), n, self.Mx, self.mode, self.temp,
                             int(self.greedy), int(self.fix_pen), self.seed.data_ptr(), t, r0,
                             self.out[r0, t].data_ptr(), ld_out, nx.data_ptr(), 5, self.done[r0:].data_ptr(),
                             self.prefix[r0, t].data_ptr(), ld_pre, self.nforced[r0:].data_ptr(),
-                            self.temps[r0:].data_ptr(),
+                            self.temps[r0:].data_ptr(), self.row_base.data_ptr(),
                             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
                         if rc != 0:
-                            raise RuntimeError("skr_mdn_sample_slabs_temps failed (%d)" % rc)
+                            raise RuntimeError("skr_mdn_sample_slabs_rows failed (%d)" % rc)
                     st.step(x, t, sample)
                     x = nx
                 cy["x%d" % i] = x
@@ -540,7 +534,7 @@ class GraphDecoder:
             nx = torch.empty(B, 5, device=self.dev)
             forced = (self.prefix[:, t], self.nforced) if self.kind == "vae" else (None, None)
             mdn_sample_device(zh.contiguous(), self.Mx, self.mode, self.temps, self.greedy, self.fix_pen, self.seed, t,
-                              self.out[:, t], nx, self.done, None, *forced)
+                              self.out[:, t], nx, self.done, None, *forced, row_base=self.row_base)
             x = nx
         cy["x"], cy["state"] = x, state
 
@@ -556,8 +550,12 @@ class GraphDecoder:
     @torch.no_grad()
     def run(self, seed: int = 0, z: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
             prefix: Optional[torch.Tensor] = None, prefix_len: Optional[torch.Tensor] = None,
-            temperature=None):
+            temperature=None, row0: int = 0):
         """Returns ``(strokes [B, N, 5], lengths [B])``.
+
+        ``row0``: row b draws the sampler noise of row ``row0 + b`` (a block of
+        a longer job list keeps its rows' noise, :mod:`.stream`). It fills a
+        device word the captured graphs read, so it never causes a recapture.
 
         ``temperature``: a float, or a vector of B values (row b samples at
         ``temperature[b]``), for this run only; None is the constructor's
@@ -594,6 +592,9 @@ class GraphDecoder:
         if labels is not None:
             self.labels.copy_(labels)
         self.seed.fill_(int(seed))
+        if int(row0) < 0 or int(row0) + self.B >= 2 ** 30:     # (the hash indexes element 4 * row + k in 32 bits)
+            raise ValueError("GraphDecoder.run: row0 must be >= 0 and row0 + batch below 2^30")
+        self.row_base.fill_(int(row0))
         ran = self.N
         if self.use_graph:
             # the graphs hold inference-cached weight copies (bf16): re-capture after a weight update
